@@ -12,9 +12,17 @@ the path has).  Scaling is weak: each rank owns `--pairs` pairs (its own index r
 Launch:  python bench.py [--gpus N --steps K --warmup W] [--config C2|C3|C4|C5]
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 Without a launcher, --gpus N > 1 spawns the N rank processes itself (before any GPU call); under
-a launcher WORLD_SIZE must equal N or the run stops.  Rank 0 prints ONE JSON line.  After the
-timed region each rank checks a stratified sample of its shard against the CPU restatement
-(`parity_sample`: the oracle as checker, never timed) and the run fails if any rank differs.
+a launcher WORLD_SIZE must equal N or the run stops.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: it generates the shard, warms up, times
+the steps and prints the line (the roofline entries come from the timed steps' own HIP events and
+the committed profiles).  `--dump-outputs DIR` also writes what the last timed step computed
+(the accumulator block and a fixed, seeded sample of the result records) as DIR/<name>.npy; the
+inputs are the same from run to run, so two builds can be compared output for output.
+`--full` adds every other leg, all after the timed region: each rank checks a stratified sample
+of its shard against the CPU restatement (`parity_sample`: the oracle as checker, never timed;
+the run fails if any rank differs), the PCIe-inclusive engine leg, the off-baseline `paths` leg,
+and at N=1 the host legs (the tool end to end and the CPU baseline).
 """
 import argparse
 import ctypes
@@ -43,6 +51,31 @@ WORKLOADS = {
     "C5": "C5: synthetic PE 2x150bp, -q -a -g -x --enable_cut_right (BASELINE.json configs[4], per GPU)",
 }
 WORKLOAD = WORKLOADS["C3"]
+DUMP_RECORDS = 1 << 20  # result records in the --dump-outputs sample (9 float32 fields each: 36 MiB)
+
+
+def sample_rows(n, k, seed=SEED):
+    """At most k of the row indices 0..n-1, ascending: one seeded pick out of each of k equal
+    strata, the first and the last row always among them.  The same (n, k, seed) gives the same rows."""
+    import numpy as np
+
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    edges = np.arange(k + 1, dtype=np.int64) * n // k
+    idx = edges[:-1] + np.random.default_rng(seed).integers(0, edges[1:] - edges[:-1])
+    idx[0], idx[-1] = 0, n - 1
+    return idx
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each array as d/<name>.npy (float32 or float64)."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(d, name + ".npy"), a)
+    log(f"outputs written to {d}: " + ", ".join(f"{k}{list(a.shape)}" for k, a in arrays.items()))
 
 
 def pmc_traffic(cfg, pairs):
@@ -527,6 +560,17 @@ class HipRunner:
     def acc_host(self):
         return self.acc.cpu().numpy().view("uint64")
 
+    def records_sample(self):
+        """--dump-outputs: a fixed sample of the last step's result records (sample_rows over this
+        rank's records), gathered on the device: (rows, one float32 column per record field)."""
+        import numpy as np
+
+        nrec = self.n * (2 if self.paired else 1)
+        idx = sample_rows(nrec, DUMP_RECORDS)
+        rows = self.results[:nrec * 16].view(nrec, 16).index_select(0, self.torch.from_numpy(idx).to(self.dev))
+        rec = rows.cpu().numpy().reshape(-1).view(np.dtype(self.abi.RESULT_DTYPE_FIELDS))
+        return idx, np.stack([rec[f].astype(np.float32) for f, _ in self.abi.RESULT_DTYPE_FIELDS], axis=1)
+
     def parity_sample(self, target):
         """CHECKER leg (after the timed region): a stratified tile sample of this rank's shard,
         the full run's records and a re-run's accumulator vs the CPU restatement (oracle/)."""
@@ -777,8 +821,17 @@ def run_rank(args):
     assert int(acc_host[abi.FQ_ACC_FILTER:abi.FQ_ACC_FILTER + 32].sum()) == reads, "FilterResult lost reads"
     acc_digest = hashlib.sha256(acc_host.tobytes()).hexdigest()
 
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed back, before any --full leg runs the engine again: the
+        # (reduced) accumulator block, every counter exact in float64, and rank 0's record sample
+        arrays = {"accumulator": acc_host.astype("float64")}
+        if hasattr(runner, "records_sample"):
+            idx, arrays["records"] = runner.records_sample()
+            arrays["record_index"] = idx.astype("float64")
+        dump_outputs(args.dump_outputs, arrays)
+
     sample = None
-    if args.sample_pairs > 0:
+    if args.full and args.sample_pairs > 0:
         t1 = time.time()
         sample = runner.parity_sample(args.sample_pairs)
         if sample is not None:
@@ -790,7 +843,7 @@ def run_rank(args):
                 sample["ranks"] = world
 
     engine = None
-    if args.engine_pairs > 0 and hasattr(runner, "engine_leg"):
+    if args.full and args.engine_pairs > 0 and hasattr(runner, "engine_leg"):
         log(f"rank {rank}: engine leg (pinned host packs of {args.engine_pairs}) ...")
         engine = runner.engine_leg(args.engine_pairs)
         log(f"rank {rank}: engine leg {engine}")
@@ -800,7 +853,8 @@ def run_rank(args):
             engine["value_all_ranks"] = round(float(t.item()), 2)
 
     paths = None
-    if rank == 0 and world == 1 and args.config == "C3" and args.paths_pairs > 0 and hasattr(runner, "paths_leg"):
+    if (args.full and rank == 0 and world == 1 and args.config == "C3" and args.paths_pairs > 0
+            and hasattr(runner, "paths_leg")):
         try:
             paths = runner.paths_leg(args.paths_pairs)
             log(f"paths {paths}")
@@ -879,7 +933,8 @@ def run_rank(args):
         "acc_sha256": acc_digest,
         "parity_sample": sample,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "C3" and hasattr(runner, "host_legs"):
+    if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "C3"
+            and hasattr(runner, "host_legs")):
         log(f"host legs: e2e on {args.e2e_pairs} pairs, CPU baseline on {args.cpu_pairs} pairs ...")
         legs = runner.host_legs(args.cpu_pairs, args.e2e_pairs, min(16, os.cpu_count() or 1))
         out["cpu_baseline"] = legs["cpu_baseline"]
@@ -938,6 +993,12 @@ def main():
     ap.add_argument("--pairs", type=int, default=None,
                     help="pairs (SE: reads) per GPU; default 100 M (BASELINE configs 1-3), 125 M for C5 "
                          "(config 4's 1 B pairs over 8 GPUs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the parity sample against the oracle, the engine leg, "
+                         "the paths leg and the host legs (e2e and CPU baseline); the options below size them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy: the accumulator block "
+                         "(float64) and a fixed, seeded sample of the result records (float32, one column per field)")
     ap.add_argument("--cpu-pairs", type=int, default=1_000_000, help="CPU-baseline sample size (pairs)")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip both host legs (e2e and CPU baseline)")
     ap.add_argument("--e2e-pairs", type=int, default=50_000_000, help="pairs of the end-to-end tool leg (0: off)")
@@ -964,6 +1025,8 @@ def main():
         args.pairs = 125_000_000 if args.config == "C5" else 100_000_000
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if not 1 <= args.read_len <= 1000:
         raise SystemExit("--read-len must be in 1..1000")
     set_read_len(args)

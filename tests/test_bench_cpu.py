@@ -44,6 +44,38 @@ def test_bench_gpus2_self_spawns_and_reduces(oracle):
     assert abs(out["value"] - 2 * 2 * PAIRS * 2 / (out["ms_per_step"] * 2 / 1e3) / 1e6) <= 1e-3 * out["value"] + 0.006  # value is rounded to 2 decimals
 
 
+def test_bench_dump_outputs_writes_the_last_steps_accumulator(oracle, tmp_path):
+    """--dump-outputs DIR: the accumulator block of the last timed step as float64 (every counter
+    exact), the same file from a second run with the same arguments; a plain run has no side legs."""
+    import bench
+    from fqtool_amd import abi
+
+    outs = []
+    for d in (tmp_path / "a", tmp_path / "b"):
+        r = run_bench("--gpus", "1", "--dump-outputs", str(d))
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+        assert line["parity_sample"] is None and line["engine"] is None and line["cpu_baseline"] is None
+        outs.append(np.load(d / "accumulator.npy"))
+    assert outs[0].dtype == np.float64 and np.array_equal(outs[0], outs[1])
+    p = bench.config_params(abi, "C3")
+    _, acc = run_oracle(oracle, p, synth_pack(oracle, PAIRS, True, first=0))
+    assert np.array_equal(outs[0], acc.astype(np.float64))
+    assert np.array_equal(outs[0].astype(np.uint64), acc)
+
+
+def test_bench_sample_rows_is_fixed_and_covers_the_ends():
+    import bench
+
+    a = bench.sample_rows(200_000_000, 1 << 20)
+    assert a.size == 1 << 20 and a[0] == 0 and a[-1] == 200_000_000 - 1
+    assert np.all(np.diff(a) > 0)
+    assert np.array_equal(a, bench.sample_rows(200_000_000, 1 << 20))
+    assert np.array_equal(bench.sample_rows(37, 64), np.arange(37))
+    assert bench.DUMP_RECORDS * (9 * 4 + 8) < 64e6  # records (float32 x 9 fields) + their indices (float64)
+
+
 def test_bench_refuses_world_size_mismatch():
     r = run_bench("--gpus", "2", env={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0
