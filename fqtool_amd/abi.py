@@ -273,6 +273,13 @@ def load_engine(path=ENGINE_LIB):
     lib.fq_kmer_close.argtypes = [vp]
     lib.fq_kmer_count.argtypes = [vp, i32, i32, i32, vp]
     lib.fq_kmer_find.argtypes = [vp, i32, i32, i32, ctypes.c_uint32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    lib.fq_deflate_bound.argtypes = [ctypes.c_size_t]
+    lib.fq_deflate_bound.restype = ctypes.c_size_t
+    lib.fq_deflate_code_lengths.argtypes = [vp, i32, i32, vp]
+    lib.fq_deflate_create.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(vp)]
+    lib.fq_deflate_destroy.argtypes = [vp]
+    lib.fq_deflate_bgzf.argtypes = [vp, vp, ctypes.c_size_t, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    lib.fq_engine_set_gz_out.argtypes = [vp, i32]
     return lib
 
 
@@ -284,6 +291,8 @@ ENGINE_SYMBOLS = [
     "fq_host_free", "fq_dup_create", "fq_dup_destroy", "fq_dup_reset", "fq_engine_set_dup", "fq_dup_merge",
     "fq_dup_stat", "fq_kmer_open", "fq_kmer_close", "fq_kmer_count", "fq_kmer_find",
     "fq_engine_raw_begin", "fq_engine_raw_enqueue", "fq_engine_raw_launch", "fq_engine_raw_wait", "fq_engine_raw_end", "fq_host_register", "fq_host_unregister",
+    "fq_deflate_bound", "fq_deflate_code_lengths", "fq_deflate_create", "fq_deflate_destroy", "fq_deflate_bgzf",
+    "fq_engine_set_gz_out",
 ]
 
 

@@ -113,6 +113,10 @@ struct fq_engine {
     std::deque<int> raw_queued;
     int raw_prev_slot = -1;
     fq_dup* dup = nullptr;    // duplication table fed by every pack (-d)
+    // device BGZF (fq_engine_set_gz_out): level 1..9, 0 = off; the compressor's scratch, one per
+    // engine (its launches all run on the compute stream, one after another)
+    int gz_level = 0;
+    fq_deflate_scratch gz;
     uint64_t calls = 0;       // order of process / process_device packs for the table
     std::string last_error;
 };
@@ -327,6 +331,7 @@ int fq_engine_destroy(fq_engine* e) {
     if (e->err) (void)hipFree(e->err);
     for (Slot& s : e->slots) free_slot(s);
     free_scratch(e->scratch);
+    fq_deflate_scratch_free(e->gz);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
     for (hipStream_t s : {e->stream, e->s_in, e->s_out, e->s_idx})
@@ -469,6 +474,21 @@ static size_t merged_cap(uint64_t text1, uint64_t text2, size_t pairs) {
     return (size_t)text1 + (size_t)text2 + 24 * pairs + kTextSlack;
 }
 
+// gz on: an output buffer takes the BGZF stream of its text in place, and the scratch covers the
+// largest text (growing it waits for the device)
+static size_t out_alloc(const fq_engine* e, size_t bytes) { return e->gz_level ? fq_deflate_bound(bytes) : bytes; }
+static int ensure_gz(fq_engine* e, size_t text_bytes) {
+    if (!e->gz_level) return FQ_OK;
+    HIP_TRY(e, fq_deflate_scratch_ensure(e->gz, text_bytes, e->cus));
+    return FQ_OK;
+}
+// mate m's output text (its length in d_total[m], at most cap bytes) -> BGZF members in place
+static int launch_gz(fq_engine* e, Slot& s, int m, size_t cap) {
+    HIP_TRY(e, fq_launch_deflate(e->gz, s.d_out[m], s.d_total + m, cap, e->gz_level, s.d_out[m], fq_deflate_bound(cap),
+                                 s.d_total + m, e->stream));
+    return FQ_OK;
+}
+
 // the output text of a text / raw pack: out1 (+ out2), or (-m) the merged stream into mate 0's buffer
 static int launch_text_out(fq_engine* e, Slot& s, int n) {
     const bool pe = e->p.paired;
@@ -502,9 +522,11 @@ static int ensure_text(fq_engine* e, Slot& s, const fq_text_batch* tb) {
             s.text_cap[m] = 0;
             const size_t cap = need + need / 8;
             HIP_TRY(e, hipMalloc(&s.d_text[m], cap));
-            HIP_TRY(e, hipMalloc(&s.d_out[m], cap));
+            HIP_TRY(e, hipMalloc(&s.d_out[m], out_alloc(e, cap)));
             s.text_cap[m] = cap;
         }
+        const int rc = ensure_gz(e, s.text_cap[m]);
+        if (rc != FQ_OK) return rc;
     }
     if ((size_t)tb->n > s.trec_cap || !s.d_total) {
         s.raw_ready = false;
@@ -665,17 +687,39 @@ int fq_engine_submit_text(fq_engine* e, const fq_text_batch* tb, fq_read_result*
     HIP_TRY(e, hipMemsetAsync(s.d_err, 0, sizeof(int), e->stream));
     if ((rc = launch(e, db, s.d_res, e->stream, s.scratch, false, false, seq_no, s.d_err)) != FQ_OK) return rc;
     if ((rc = launch_text_out(e, s, tb->n)) != FQ_OK) return rc;
+    size_t tback[2] = {0, 0};
+    for (int m = 0; m < (mrg ? 1 : pe ? 2 : 1); ++m) {
+        tback[m] = mrg ? merged_cap(tb->text_bytes[0], tb->text_bytes[1], (size_t)tb->n) : tb->text_bytes[m] + kTextSlack;
+        if (e->gz_level && (rc = launch_gz(e, s, m, tback[m])) != FQ_OK) return rc;
+    }
+    const size_t nres = (size_t)tb->n * (pe ? 2 : 1);
+    if (e->gz_level) {
+        // gz: a bound of the stream would be more than the text, so the sizes come back first and
+        // the copy back is exactly the members, as for raw packs (issue_copies)
+        HIP_TRY(e, hipMemsetAsync(s.d_total + 2, 0, 2 * sizeof(unsigned long long), e->stream));  // (no adapter entries)
+        HIP_TRY(e, hipMemcpyAsync(results, s.d_res, nres * sizeof(fq_read_result), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(e, hipMemcpyAsync(s.h_total, s.d_total, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(e, hipMemcpyAsync(s.h_err, s.d_err, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(e, hipEventRecord(s.ev_kern, e->stream));
+        for (int m = 0; m < 2; ++m) {
+            const bool has = m < (mrg ? 1 : pe ? 2 : 1);
+            s.copy_dst[m] = has ? out->text[m] : nullptr;
+            s.copy_cap[m] = has ? fq_deflate_bound(tback[m]) : 0;
+        }
+        s.copy_pending = true;
+        s.busy = true;
+        s.text_out = out;
+        e->pending.push_back(Pending{seq_no, k, false, 0});
+        return issue_copies(e, -1);
+    }
     HIP_TRY(e, hipEventRecord(s.ev_kern, e->stream));
     // D2H: records, output sizes and text (the text up to its input span: an upper bound of the
     // output, no device-to-host round trip for the exact size), the error word
     HIP_TRY(e, hipStreamWaitEvent(e->s_out, s.ev_kern, 0));
-    const size_t nres = (size_t)tb->n * (pe ? 2 : 1);
     HIP_TRY(e, hipMemcpyAsync(results, s.d_res, nres * sizeof(fq_read_result), hipMemcpyDeviceToHost, e->s_out));
     HIP_TRY(e, hipMemcpyAsync(s.h_total, s.d_total, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->s_out));
-    for (int m = 0; m < (mrg ? 1 : pe ? 2 : 1); ++m) {
-        const size_t back = mrg ? merged_cap(tb->text_bytes[0], tb->text_bytes[1], (size_t)tb->n) : tb->text_bytes[m] + kTextSlack;
-        HIP_TRY(e, hipMemcpyAsync(out->text[m], s.d_out[m], back, hipMemcpyDeviceToHost, e->s_out));
-    }
+    for (int m = 0; m < (mrg ? 1 : pe ? 2 : 1); ++m)
+        HIP_TRY(e, hipMemcpyAsync(out->text[m], s.d_out[m], tback[m], hipMemcpyDeviceToHost, e->s_out));
     HIP_TRY(e, hipMemcpyAsync(s.h_err, s.d_err, sizeof(int), hipMemcpyDeviceToHost, e->s_out));
     HIP_TRY(e, hipEventRecord(s.ev_done, e->s_out));
     s.busy = true;
@@ -713,7 +757,9 @@ static int ensure_raw(fq_engine* e, Slot& s) {
         HIP_TRY(e, hipMalloc(&s.d_text[m], text));
         // (+ the adapter entries' slack; -m: mate 0's takes the merged stream of both mates' text)
         const size_t out = pe && m == 0 && e->p.merge_enabled ? merged_cap(text, text, recs) + 3 * recs + 64 : text + 4 * recs + 64;
-        HIP_TRY(e, hipMalloc(&s.d_out[m], out));
+        HIP_TRY(e, hipMalloc(&s.d_out[m], out_alloc(e, out)));
+        const int rc = ensure_gz(e, out);
+        if (rc != FQ_OK) return rc;
         HIP_TRY(e, hipMalloc(&s.d_trec[m], recs * sizeof(fq_text_rec)));
         HIP_TRY(e, hipMalloc(&s.d_tsize[m], recs * sizeof(uint32_t)));
         HIP_TRY(e, hipMalloc(&s.d_toff[m], recs * sizeof(uint32_t)));
@@ -852,6 +898,7 @@ int fq_engine_raw_wait(fq_engine* e, fq_raw_result* r) {
 int fq_engine_raw_launch(fq_engine* e, fq_raw_result* r, fq_raw_out* out, uint64_t seq_no) {
     if (!e || !r || !out) return FQ_E_INVALID;
     if (e->raw_queued.empty()) return fail(e, FQ_E_INVALID, "fq_engine_raw_launch without an enqueued window");
+    if (e->gz_level && out->results) return fail(e, FQ_E_INVALID, "raw pack: records-only egress while gz output is on");
     HIP_TRY(e, hipSetDevice(e->device));
     const int k = e->raw_queued.front();
     e->raw_queued.pop_front();
@@ -913,6 +960,12 @@ int fq_engine_raw_launch(fq_engine* e, fq_raw_result* r, fq_raw_out* out, uint64
     for (int m = 0; m < mates; ++m) back[m] = (size_t)r->text_bytes[m] + kTextSlack + 3 * (size_t)n;
     if (mrg) back[0] = merged_cap(r->text_bytes[0], r->text_bytes[1], (size_t)n) + 3 * (size_t)n;
     if ((rc = launch_text_out(e, s, n)) != FQ_OK) return rc;
+    // gz: each mate's text becomes BGZF members in place (d_total[m]: their bytes); the entries
+    // follow them as they follow the text (members + entries <= the bound of text + entries)
+    for (int m = 0; m < mates && e->gz_level; ++m) {
+        if ((rc = launch_gz(e, s, m, back[m])) != FQ_OK) return rc;
+        back[m] = fq_deflate_bound(back[m]);
+    }
     for (int m = 0; m < mates; ++m) {
         if (e->p.adapter_trimming)
             HIP_TRY(e, fq_launch_raw_adapters(s.d_text[m], s.d_trec[m], s.d_res, n, pe ? 1 : 0, m, s.d_tsize[m], s.d_toff[m],
@@ -943,6 +996,27 @@ int fq_engine_raw_end(fq_engine* e) {
     e->raw_queued.clear();
     e->raw_prev_slot = -1;
     e->raw = false;
+    return FQ_OK;
+}
+
+int fq_engine_set_gz_out(fq_engine* e, int32_t level) {
+    if (!e) return FQ_E_INVALID;
+    if (level < 0 || level > 9) return fail(e, FQ_E_INVALID, "fq_engine_set_gz_out: level must be 0 (off) or 1..9");
+    if (!e->pending.empty() || !e->raw_queued.empty())
+        return fail(e, FQ_E_INVALID, "fq_engine_set_gz_out with packs in flight");
+    if ((level != 0) != (e->gz_level != 0)) {
+        // the output buffers are sized for the stream's bound while gz is on: re-made on next use
+        for (Slot& s : e->slots) {
+            s.text_cap[0] = s.text_cap[1] = 0;
+            s.raw_ready = false;
+        }
+        if (!level) {
+            HIP_TRY(e, hipSetDevice(e->device));
+            HIP_TRY(e, hipDeviceSynchronize());
+            fq_deflate_scratch_free(e->gz);
+        }
+    }
+    e->gz_level = level;
     return FQ_OK;
 }
 

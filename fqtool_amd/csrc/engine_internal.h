@@ -51,6 +51,24 @@ hipError_t fq_launch_merge_out(const char* d_text1, const char* d_text2, const f
                                const fq_text_rec* d_rec2, const fq_read_result* d_res, int n, int discard,
                                uint32_t* d_size, uint32_t* d_off, void* d_temp, size_t temp_bytes, char* d_out,
                                unsigned long long* d_total, hipStream_t s);
+// Device BGZF (deflate.hip): scratch of the compressor, shared by the launches of one stream (they
+// run one after another): a token array per resident workgroup, a 64 KiB slot and a size per member
+struct fq_deflate_scratch {
+    uint32_t* tok = nullptr;
+    uint8_t* slots = nullptr;
+    uint32_t* sizes = nullptr;
+    unsigned long long* total = nullptr;
+    size_t members = 0;  // members the slots hold
+    int grid = 0;        // workgroups the token arrays serve
+    int cus = 0;
+};
+// grows the scratch to texts of max_bytes (freeing the old buffers waits for the device)
+hipError_t fq_deflate_scratch_ensure(fq_deflate_scratch& sc, size_t max_bytes, int cus);
+void fq_deflate_scratch_free(fq_deflate_scratch& sc);
+// d_text[0, min(*d_n, cap_bytes)) -> BGZF members at d_dst (which may be d_text: the members are
+// compacted only after all are compressed), their bytes to *d_total (which may be d_n)
+hipError_t fq_launch_deflate(const fq_deflate_scratch& sc, const void* d_text, const unsigned long long* d_n, size_t cap_bytes,
+                             int level, void* d_dst, size_t dst_cap, unsigned long long* d_total, hipStream_t s);
 // Raw FASTQ streams (raw.hip): per (window, mate) device state of the record indexing
 struct fq_raw_state {
     uint32_t text_start;  // buffer offset of the window's text (the carried bytes first)

@@ -1227,6 +1227,7 @@ void Pool::run(int n, const std::function<void(int)>& fn) {
 void Pack::clear() {
     n = 0;
     raw = false;
+    gz_members = false;
     recs = false;
     zc = false;
     segs[0].clear();
@@ -1734,6 +1735,14 @@ void Writer::write_raw(const char* p, size_t n, Pool* pool) {
         any_member_ = true;
     }
     if (writing.valid()) writing.get();
+}
+
+void Writer::write_members(const char* p, size_t n) {
+    if (!fp_) throw std::runtime_error("write to a closed output");
+    if (!gzip_) throw std::runtime_error("gzip members go to gzip outputs only");
+    if (!n) return;
+    if (std::fwrite(p, 1, n, fp_) != n) throw std::runtime_error(std::string("write failed: ") + std::strerror(errno));
+    any_member_ = true;
 }
 
 void Writer::write_segs(const iovec* v, size_t n) {

@@ -281,6 +281,7 @@ struct Pack {
     // FASTQ-text pack (fq_engine_submit_text, pack_text): each mate's text span (inside its arena or
     // the file mapping), the per-record index into it, and the output text the engine writes back
     bool text_mode = false;
+    bool gz_members = false;  // the engine compressed the output text: out_text holds BGZF members
     const char* span[2] = {nullptr, nullptr};
     uint64_t span_bytes[2] = {0, 0};
     PodBuf<fq_text_rec> trec[2];
@@ -386,6 +387,8 @@ class Writer {
     void write(const std::string& s) { write(std::vector<std::string>{s}); }
     // n bytes from p as they are (gzip: in blocks compressed in parallel on the pool)
     void write_raw(const char* p, size_t n, Pool* pool = nullptr);
+    // gzip outputs only: n bytes of complete gzip members (the engine's device BGZF), as they are
+    void write_members(const char* p, size_t n);
     // plain outputs only: the byte ranges in order (writev)
     void write_segs(const iovec* v, size_t n);
     bool gzip() const { return gzip_; }

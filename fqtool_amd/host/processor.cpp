@@ -27,6 +27,11 @@
 #include "evaluator.h"
 #include "pargz.h"
 
+// Device BGZF (FQ_GZ_DEVICE=1) is bound weakly: an engine library without it (the CPU stand-ins of
+// the test builds) links all the same, and the tool then compresses on the host as before.
+#pragma weak fq_engine_set_gz_out
+#pragma weak fq_deflate_bound
+
 namespace fqhost {
 namespace {
 
@@ -488,12 +493,13 @@ class AsyncWriter {
         if (failed_) std::rethrow_exception(error());
         bool any = false;
         for (const auto& s : blocks) any = any || !s.empty();
-        if (any && !q_.push(Job{std::move(blocks), nullptr, 0, nullptr, nullptr}) && failed_) std::rethrow_exception(error());
+        if (any && !q_.push(Job{std::move(blocks), nullptr, 0, nullptr, nullptr, false}) && failed_) std::rethrow_exception(error());
     }
     // queue n bytes at p (which stay valid until `done` runs); the writer thread runs it once the
-    // bytes are written (or dropped after a write error)
-    void write_raw(const char* p, size_t n, std::function<void()> done) {
-        if (failed_ || !q_.push(Job{{}, p, n, done, nullptr})) {
+    // bytes are written (or dropped after a write error); members: the bytes are complete gzip
+    // members (the engine's device BGZF), written as they are
+    void write_raw(const char* p, size_t n, std::function<void()> done, bool members = false) {
+        if (failed_ || !q_.push(Job{{}, p, n, done, nullptr, members})) {
             done();  // (the writer has stopped: nothing will take the text)
             if (failed_) std::rethrow_exception(error());
             throw std::runtime_error("write to a closed output");
@@ -501,7 +507,7 @@ class AsyncWriter {
     }
     // queue byte ranges (plain outputs; they stay valid until `done` runs), as write_raw
     void write_segs(const std::vector<iovec>* segs, std::function<void()> done) {
-        if (failed_ || !q_.push(Job{{}, nullptr, 0, done, segs})) {
+        if (failed_ || !q_.push(Job{{}, nullptr, 0, done, segs, false})) {
             done();
             if (failed_) std::rethrow_exception(error());
             throw std::runtime_error("write to a closed output");
@@ -534,6 +540,7 @@ class AsyncWriter {
         size_t raw_n;
         std::function<void()> done;
         const std::vector<iovec>* segs = nullptr;
+        bool members = false;
     };
     struct Io {
         uint64_t off;
@@ -577,6 +584,7 @@ class AsyncWriter {
                 } else if (j.done) {
                     try {
                         if (j.segs) w_.write_segs(j.segs->data(), j.segs->size());
+                        else if (j.members) w_.write_members(j.raw, j.raw_n);
                         else w_.write_raw(j.raw, j.raw_n, pool_);
                     } catch (...) {
                         j.done();
@@ -648,7 +656,7 @@ void OutputSet::write(PackOutput&& out) {
     if (wu2_) wu2_->write(std::move(out.unpaired2));
 }
 
-void OutputSet::write_text(const char* t1, size_t n1, const char* t2, size_t n2, std::function<void()> done) {
+void OutputSet::write_text(const char* t1, size_t n1, const char* t2, size_t n2, std::function<void()> done, bool members) {
     if (!(w1_ && (!paired_ || w2_))) {  // PE writes the pair outputs only with both writers (:469)
         done();
         return;
@@ -660,13 +668,13 @@ void OutputSet::write_text(const char* t1, size_t n1, const char* t2, size_t n2,
     };
     std::exception_ptr err;
     try {
-        w1_->write_raw(t1, n1, fin);
+        w1_->write_raw(t1, n1, fin, members);
     } catch (...) {
         err = std::current_exception();
     }
     if (w2_) {
         try {
-            w2_->write_raw(t2, n2, fin);
+            w2_->write_raw(t2, n2, fin, members);
         } catch (...) {
             if (!err) err = std::current_exception();
         }
@@ -701,12 +709,12 @@ void OutputSet::write_text_segs(const std::vector<iovec>& s1, const std::vector<
 
 bool OutputSet::plain_pair_outputs() const { return (!w1_ || !w1_->gzip()) && (!w2_ || !w2_->gzip()); }
 
-void OutputSet::write_merged_text(const char* t, size_t n, std::function<void()> done) {
+void OutputSet::write_merged_text(const char* t, size_t n, std::function<void()> done, bool members) {
     if (!wm_) {
         done();
         return;
     }
-    wm_->write_raw(t, n, std::move(done));
+    wm_->write_raw(t, n, std::move(done), members);
 }
 
 void OutputSet::close() {
@@ -915,8 +923,10 @@ bool Sink::plain_pair_outputs() const { return outs_ && !merge_ && outs_->plain_
 void Sink::consume_text(const Pack& pk, std::function<void()> done) {
     pairs_ += (uint64_t)pk.n;
     if (pk.zc) outs_->write_text_segs(pk.segs[0], pk.segs[1], std::move(done));
-    else if (merge_) outs_->write_merged_text(pk.out_text[0].data(), pk.tout.bytes[0], std::move(done));
-    else outs_->write_text(pk.out_text[0].data(), pk.tout.bytes[0], pk.out_text[1].data(), pk.tout.bytes[1], std::move(done));
+    else if (merge_) outs_->write_merged_text(pk.out_text[0].data(), pk.tout.bytes[0], std::move(done), pk.gz_members);
+    else
+        outs_->write_text(pk.out_text[0].data(), pk.tout.bytes[0], pk.out_text[1].data(), pk.tout.bytes[1], std::move(done),
+                          pk.gz_members);
 }
 
 void Sink::close() {
@@ -1367,6 +1377,9 @@ struct Lane {
     int dev, depth;
     fq_engine* e = nullptr;
     fq_dup* dup = nullptr;  // -d: this engine's table, kept across re-creation
+    int gz_level = 0;       // FQ_GZ_DEVICE=1 with .gz outputs: text / raw packs come back as BGZF members
+    // an output buffer of x bytes of text, sized for its members instead
+    size_t out_cap(size_t x) const { return gz_level ? fq_deflate_bound(x) : x; }
     int max_cycles = 0, max_batch = 0, max_stride = 0;
     Queue<std::unique_ptr<Pack>> in, out;
     std::deque<std::unique_ptr<Pack>> inflight;  // submission order == input order
@@ -1388,6 +1401,8 @@ struct Lane {
             if (fq_engine_set_dup(e, dup) != FQ_OK)
                 throw std::runtime_error(std::string("fq_engine_set_dup: ") + fq_engine_last_error(e));
         }
+        if (gz_level && fq_engine_set_gz_out(e, gz_level) != FQ_OK)
+            throw std::runtime_error(std::string("fq_engine_set_gz_out: ") + fq_engine_last_error(e));
         max_cycles = cycles;
         max_batch = batch;
         max_stride = stride;
@@ -1433,6 +1448,14 @@ struct Lane {
                 tb.text[m] = pk.span[m];
                 tb.text_bytes[m] = pk.span_bytes[m];
                 tb.rec[m] = pk.trec[m].data();
+            }
+            if (gz_level) {  // (room for the members of the output text)
+                for (int m = 0; m < (pk.paired ? 2 : 1); ++m)
+                    if (pk.tout.text[m]) {
+                        pk.out_text[m].resize_uninit(out_cap(pk.out_text[m].size()));
+                        pk.tout.text[m] = pk.out_text[m].data();
+                    }
+                pk.gz_members = true;
             }
             if (fq_engine_submit_text(e, &tb, pk.results(), &pk.tout, pk.seq_no) != FQ_OK)
                 throw std::runtime_error(std::string("fq_engine_submit_text: ") + fq_engine_last_error(e));
@@ -1522,7 +1545,7 @@ struct Lane {
         // the formatter writes the output from the staging window, which then keeps the carry
         // capacity free in front of the window bytes (the device buffer's layout)
         const char* eg_env = std::getenv("FQ_RAW_EGRESS");
-        const bool recs = !merge && eg_env && std::string(eg_env) == "host";
+        const bool recs = !merge && !gz_level && eg_env && std::string(eg_env) == "host";
         const uint64_t off0 = recs ? ccap : 0;
         const int raw_depth = 4;  // packs launched and not yet polled
         const size_t raw_ahead = 3;  // windows enqueued ahead of their launch (the copy-in queue)
@@ -1772,10 +1795,12 @@ struct Lane {
                                 cap = (size_t)(cin[0] + w.n[0] + cin[1] + w.n[1] + 28 * (uint64_t)target + 64);
                             // (1/8 headroom when the page-locked buffer is first made or outgrown:
                             // windows vary by a few percent, and a regrowth registers anew)
+                            cap = out_cap(cap);
                             pk->out_text[m].reserve(cap + cap / 8);
                             pk->out_text[m].resize_uninit(cap);
                             pk->rout.text.text[m] = m < mates ? pk->out_text[m].data() : nullptr;
                         }
+                        pk->gz_members = gz_level != 0;
                     }
                     fq_raw_result r{};
                     const auto e0 = std::chrono::steady_clock::now();
@@ -2049,10 +2074,12 @@ struct Lane {
                     size_t cap = m < R.mates ? (size_t)(w.n[m] + 4 * (uint64_t)target + 64) : 0;
                     if (merge && m == 0)  // (-m: the merged stream of both mates' text)
                         cap = (size_t)(w.n[0] + w.n[1] + 28 * (uint64_t)target + 64);
+                    cap = out_cap(cap);
                     pk->out_text[m].reserve(cap + cap / 8);  // (headroom: see run_raw)
                     pk->out_text[m].resize_uninit(cap);
                     pk->rout.text.text[m] = m < R.mates ? pk->out_text[m].data() : nullptr;
                 }
+                pk->gz_members = gz_level != 0;
                 const auto e0 = std::chrono::steady_clock::now();
                 if (fq_engine_raw_launch(e, &r, &pk->rout, w.id) != FQ_OK) {  // (r as fq_engine_raw_wait gave it)
                     throw std::runtime_error(std::string("fq_engine_raw_launch: ") + fq_engine_last_error(e));
@@ -2329,8 +2356,16 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
             for (int m = 0; m < (paired ? 2 : 1); ++m)
                 if ((pre_gz[m] = ParGzSource::open(files[m], (size_t)1 << 20, gz_inflate_threads()))) pre_gz[m]->prefetch();
         }
+        // FQ_GZ_DEVICE=1: the engines compress the output text of text / raw packs (BGZF members, -z
+        // as the level) when every output those packs feed is .gz; host packs, and engines without
+        // the call, keep the host's compression
+        const char* gzd_env = std::getenv("FQ_GZ_DEVICE");
+        const bool gz_device = gzd_env && std::string(gzd_env) == "1" && fq_engine_set_gz_out && fq_deflate_bound &&
+                               text_mode && o.compression >= 1 && o.compression <= 9 &&
+                               (o.merge ? ends_with_gz(o.merge_out) : ends_with_gz(o.out1) && (!paired || ends_with_gz(o.out2)));
         for (int g = 0; g < G; ++g) {
             lanes.emplace_back(new Lane(devices[(size_t)g], depth));
+            lanes.back()->gz_level = gz_device ? o.compression : 0;
             lanes.back()->t_start = t0;
             lanes.back()->merge = o.merge && paired;
             lanes.back()->make(o, cyc0, (int)pack_n, stride0);

@@ -36,12 +36,13 @@ class OutputSet {
     void write(PackOutput&& out);
     // out1 / out2 text as is (waits until both writers have taken it)
     // queue engine-assembled output text of both mates; `done` runs once both are written
-    void write_text(const char* t1, size_t n1, const char* t2, size_t n2, std::function<void()> done);
+    // (members: the bytes are gzip members the engine compressed, for .gz outputs, written as is)
+    void write_text(const char* t1, size_t n1, const char* t2, size_t n2, std::function<void()> done, bool members = false);
     // the same as byte ranges (plain outputs: writev); the ranges stay valid until `done` runs
     void write_text_segs(const std::vector<iovec>& s1, const std::vector<iovec>& s2, std::function<void()> done);
     bool plain_pair_outputs() const;  // out1 / out2 (those that exist) are not gzip
     // -m: a text pack's merged stream (the merged output; out1 / out2 get nothing)
-    void write_merged_text(const char* t, size_t n, std::function<void()> done);
+    void write_merged_text(const char* t, size_t n, std::function<void()> done, bool members = false);
     void close();  // flushes and closes every file
 
    private:

@@ -526,6 +526,44 @@ int fq_kmer_count(fq_kmer_set* s, int32_t keylen, int32_t first, int32_t shift_t
 int fq_kmer_find(fq_kmer_set* s, int32_t keylen, int32_t first, int32_t shift_tail, uint32_t seed, uint64_t* occ,
                  size_t cap, size_t* n_out);
 
+/* ---- device BGZF: output text compressed on the GPU ---------------------------------------------
+ * A span of text in device memory is cut into members of FQ_BGZF_IN input bytes (the last one
+ * shorter; no bytes, no member).  Each member is a complete BGZF member laid out as the host
+ * writer's: the 18-byte header "1f 8b 08 04 00000000 XFL ff 0600 'B' 'C' 0200 BSIZE-1", one
+ * deflate block (dynamic Huffman over an LZ77 parse, or stored when that is not smaller), CRC32
+ * and ISIZE.  XFL is 4 in members the device wrote and 0 in the host writer's, which is how a file
+ * tells which side compressed a member (BGZF readers do not look at it).  A member is never
+ * larger than its input + 31, so a stream of n bytes never exceeds fq_deflate_bound(n).
+ * level 1..9 selects the search effort (1-3: the hash table of earlier positions and runs;
+ * 4-9: also a second look-up among the nearest 256 positions); every level gives a valid stream.
+ * fq_deflate_bgzf refuses (FQ_E_INVALID, nothing written) n > max_bytes, a level outside 1..9 and
+ * out_cap < fq_deflate_bound(n).
+ * fq_engine_set_gz_out (only while no pack is pending or enqueued, else FQ_E_INVALID) with level
+ * 1..9 makes text packs (fq_engine_submit_text) and raw packs (fq_engine_raw_launch) compress
+ * their output text on the device, on the compute stream behind the text kernel: out->text[m]
+ * then receives BGZF members and out->bytes[m] is their byte count (-m: the merged stream in
+ * text[0] likewise); raw packs' adapter entries still follow, uncompressed, at text[m] + bytes[m].
+ * The caller's out->text[m] must then hold fq_deflate_bound(x), x being the size documented for
+ * the plain case (text packs: text_bytes + 16, -m: both + 24 * n + 16; raw packs: carry capacity
+ * + window bytes + 4 * max_batch + 16, -m: both mates' + 28 * max_batch + 64); the copy back is
+ * exactly the members (text packs too: their sizes come back first, as raw packs').  Records-only
+ * egress (out->results set) is refused while gz is on.  Level 0 (the default) turns it off;
+ * fq_engine_submit and fq_engine_process* are unaffected.  The device scratch is allocated with
+ * the slots' output buffers, nothing while gz is off.
+ * fq_deflate_code_lengths runs the kernels' own length builder on the host (optimal length-limited
+ * code lengths by package-merge: 0 for unused symbols; n_sym <= 288, max_len <= 15, the sum of
+ * freq times max_len below 2^32, else FQ_E_INVALID). */
+#define FQ_BGZF_IN 65280
+size_t fq_deflate_bound(size_t n);      /* n + 31 * ceil(n / 65280): every member stored; 0 for 0; no device needed */
+int fq_deflate_code_lengths(const uint32_t* freq, int32_t n_sym, int32_t max_len, uint8_t* len);
+                                        /* the kernels' own length builder, run on the host (checks, tests); no device needed */
+typedef struct fq_deflate fq_deflate;
+int fq_deflate_create(int device, size_t max_bytes, fq_deflate** out);  /* FQ_E_NO_DEVICE as fq_engine_create */
+int fq_deflate_destroy(fq_deflate* d);
+int fq_deflate_bgzf(fq_deflate* d, const void* text, size_t n, int32_t level,
+                    void* out, size_t out_cap, size_t* out_bytes);     /* host pointers, synchronous */
+int fq_engine_set_gz_out(fq_engine* e, int32_t level);                  /* 0 (default): off */
+
 /* Kernel timing of the engine's last process_device call (HIP events on the launch stream),
  * in milliseconds; 0 when unavailable. */
 double fq_engine_last_kernel_ms(const fq_engine* e);
