@@ -109,6 +109,17 @@ class FqTextOut(ctypes.Structure):
     _fields_ = [("text", ctypes.c_void_p * 2), ("bytes", ctypes.c_uint64 * 2)]
 
 
+FQ_E_NO_DEVICE = -2
+FQ_INFLATE_MAX = 65536
+FQ_INFL_OK, FQ_INFL_DATA, FQ_INFL_LONG, FQ_INFL_SHORT, FQ_INFL_CRC = 0, 1, 2, 3, 4
+
+
+class FqInflateMember(ctypes.Structure):  # fq_inflate_member, 32 bytes
+    _fields_ = [("in_off", ctypes.c_uint64), ("in_len", ctypes.c_uint32), ("isize", ctypes.c_uint32),
+                ("crc", ctypes.c_uint32), ("status", ctypes.c_uint32), ("produced", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32)]
+
+
 class FqRawWindow(ctypes.Structure):  # fq_raw_window
     _fields_ = [("bytes", ctypes.c_void_p * 2), ("n", ctypes.c_uint64 * 2)]
 
@@ -280,6 +291,13 @@ def load_engine(path=ENGINE_LIB):
     lib.fq_deflate_destroy.argtypes = [vp]
     lib.fq_deflate_bgzf.argtypes = [vp, vp, ctypes.c_size_t, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     lib.fq_engine_set_gz_out.argtypes = [vp, i32]
+    cs = ctypes.c_size_t
+    lib.fq_inflate_create.argtypes = [ctypes.c_int, cs, cs, cs, ctypes.POINTER(vp)]
+    lib.fq_inflate_destroy.argtypes = [vp]
+    lib.fq_inflate_members.argtypes = [vp, vp, cs, ctypes.POINTER(FqInflateMember), cs, vp, cs, ctypes.POINTER(cs)]
+    lib.fq_inflate_bgzf.argtypes = [vp, vp, cs, vp, cs, ctypes.POINTER(cs), ctypes.POINTER(ctypes.c_int64)]
+    lib.fq_inflate_last_kernel_ms.argtypes = [vp]
+    lib.fq_inflate_last_kernel_ms.restype = ctypes.c_double
     return lib
 
 
@@ -293,6 +311,7 @@ ENGINE_SYMBOLS = [
     "fq_engine_raw_begin", "fq_engine_raw_enqueue", "fq_engine_raw_launch", "fq_engine_raw_wait", "fq_engine_raw_end", "fq_host_register", "fq_host_unregister",
     "fq_deflate_bound", "fq_deflate_code_lengths", "fq_deflate_create", "fq_deflate_destroy", "fq_deflate_bgzf",
     "fq_engine_set_gz_out",
+    "fq_inflate_create", "fq_inflate_destroy", "fq_inflate_members", "fq_inflate_bgzf", "fq_inflate_last_kernel_ms",
 ]
 
 

@@ -25,6 +25,12 @@
 #include <mutex>
 #include <stdexcept>
 
+// Device inflate (FQ_GZ_IN_DEVICE=1) is bound weakly: an engine library without it (the CPU stand-ins
+// of the test builds) links all the same, and BGZF inputs are then inflated on the host as before.
+#pragma weak fq_inflate_create
+#pragma weak fq_inflate_destroy
+#pragma weak fq_inflate_members
+
 namespace fqhost {
 
 namespace {
@@ -309,9 +315,17 @@ bool FqReader::read(std::string& name, std::string& seq, std::string& strand, st
 // member's bytes that zlib had written out before its CRC / ISIZE check or its data error.  Here the
 // bytes of a batch are handed out only up to the last call boundary before the batch's end until
 // the next batch is known to be good, so the cut can fall anywhere before a bad member.
+//
+// FQ_GZ_IN_DEVICE=1 (and an engine library that has the inflate calls, and no member above
+// FQ_INFLATE_MAX): a batch's members are first given to the device (fq_inflate_members, one handle
+// per source since the mates read on their own threads, made at the first batch and sized for one
+// batch), straight from the file mapping into the batch's buffer.  Only a batch the device inflates
+// whole and finds good is taken from it; anything else (a bad member, a refusal, a HIP error, a
+// failed create) runs the zlib code below on the same members unchanged, so where a corrupt stream
+// ends is decided by zlib alone.  After a HIP error the source stops trying the device.
 class BgzfSource {
    public:
-    static std::unique_ptr<BgzfSource> open(const std::string& path, size_t call) {
+    static std::unique_ptr<BgzfSource> open(const std::string& path, size_t call, int gz_device = -1) {
         const int fd = ::open(path.c_str(), O_RDONLY);
         if (fd < 0) return nullptr;
         struct stat st;
@@ -326,6 +340,12 @@ class BgzfSource {
                                                      std::max<size_t>(call, 1)));
         if (!b->walk()) return nullptr;
         madvise(m, (size_t)st.st_size, MADV_SEQUENTIAL);
+        b->path_ = path;
+        const char* dv = getenv("FQ_GZ_IN_DEVICE");
+        b->device_ = dv && std::string(dv) == "1" && gz_device >= 0 && fq_inflate_create && fq_inflate_destroy &&
+                             fq_inflate_members && b->device_fits_
+                         ? gz_device
+                         : -1;
         return b;
     }
     // up to `want` more bytes of the decompressed stream into dst; false on corrupt data, once the
@@ -371,6 +391,11 @@ class BgzfSource {
     }
     ~BgzfSource() {
         if (ahead_.valid()) ahead_.wait();
+        // (FQ_TIMING keeps the tool's teardown, so this is reached; no batch is inflating any more)
+        if (getenv("FQ_TIMING") && started_)
+            fprintf(stderr, "bgzf input %s: %zu members inflated on the device, %zu on the host\n", path_.c_str(), dev_members_,
+                    host_members_);
+        if (infl_) fq_inflate_destroy(infl_);
         munmap(const_cast<unsigned char*>(map_), size_);
     }
 
@@ -412,6 +437,7 @@ class BgzfSource {
             if (h[3] & 2) p += 2;    // FHCRC
             if (!bsize || bsize > size_ - o || p + 8 > bsize) return false;
             members_.push_back(Member{o + p, bsize - p - 8, le32(h + bsize - 8), le32(h + bsize - 4)});
+            if (members_.back().clen > FQ_INFLATE_MAX || members_.back().isize > FQ_INFLATE_MAX) device_fits_ = false;
             o += bsize;
         }
         return !members_.empty();
@@ -443,25 +469,75 @@ class BgzfSource {
     // threads.  A member that fails its inflate, CRC32 or ISIZE check ends the stream: b.keep is
     // the start of the reference's gzread call that meets the failure (the bytes before it, the bad
     // member's included, are in b.data).
+    // (FQ_BGZF_BATCH: a smaller batch, for the tests of cuts across batches)
+    static size_t batch_bytes() {
+        const char* be = getenv("FQ_BGZF_BATCH");
+        return be && atoll(be) > 0 ? (size_t)atoll(be) : (size_t)64 << 20;
+    }
+    // The batch that starts at member i ends before member batch_end (out = its output bytes): ~64 MB
+    // of output, and on the device route at most 1024 members, which is what an MI355X holds in
+    // flight (a 64 MB batch of 65280-byte members has 1029: a second round for five members).
+    size_t batch_end(size_t i, size_t& out) const {
+        const size_t kBatch = batch_bytes(), kDeviceMembers = 1024;
+        size_t j = i;
+        out = 0;
+        while (j < members_.size() && (out < kBatch || j == i) && (device_ < 0 || j - i < kDeviceMembers)) out += members_[j++].isize;
+        return j;
+    }
+    // members [first, end) on the device into dst (total bytes): true only if all of them are good
+    bool inflate_on_device(size_t first, size_t end, char* dst, size_t total) {
+        if (device_ < 0) return false;
+        if (!infl_) {
+            // sized for the largest batch of this file: the batches are cut as inflate_batch cuts them
+            size_t max_in = 0, max_out = 0, max_n = 0;
+            for (size_t i = 0; i < members_.size();) {
+                size_t out = 0;
+                const size_t j = batch_end(i, out);
+                max_in = std::max(max_in, members_[j - 1].data + members_[j - 1].clen - members_[i].data);
+                max_out = std::max(max_out, out);
+                max_n = std::max(max_n, j - i);
+                i = j;
+            }
+            if (fq_inflate_create(device_, max_in, max_out, max_n, &infl_) != FQ_OK) {
+                infl_ = nullptr;
+                device_ = -1;
+                return false;
+            }
+        }
+        const size_t base = members_[first].data;
+        desc_.resize(end - first);
+        for (size_t i = first; i < end; ++i) {
+            fq_inflate_member& d = desc_[i - first];
+            std::memset(&d, 0, sizeof d);
+            d.in_off = members_[i].data - base;
+            d.in_len = (uint32_t)members_[i].clen;
+            d.isize = members_[i].isize;
+            d.crc = members_[i].crc;
+        }
+        size_t n_bad = 0;
+        const int rc = fq_inflate_members(infl_, map_ + base, members_[end - 1].data + members_[end - 1].clen - base, desc_.data(),
+                                          desc_.size(), dst, total, &n_bad);
+        if (rc == FQ_E_HIP) device_ = -1;  // (the handle is destroyed with the source)
+        return rc == FQ_OK && n_bad == 0;
+    }
     void inflate_batch(Batch& b) {
         static const int kThreads = (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency() / 2));
         const size_t first = next_member_;
-        size_t end = first, total = 0;
+        size_t total = 0;
+        const size_t end = batch_end(first, total);
         std::vector<size_t> at;
-        // (FQ_BGZF_BATCH: a smaller batch, for the tests of cuts across batches)
-        const char* be = getenv("FQ_BGZF_BATCH");
-        const size_t kBatch = be && atoll(be) > 0 ? (size_t)atoll(be) : (size_t)64 << 20;
-        while (end < members_.size() && (total < kBatch || end == first)) {
-            at.push_back(total);
-            total += members_[end].isize;
-            ++end;
-        }
+        for (size_t i = first, o = 0; i < end; o += members_[i++].isize) at.push_back(o);
         b.data.resize(total);
         b.base = stream_off_;
         const size_t cnt = end - first;
         next_member_ = end;
         stream_off_ += total;
         b.last = end >= members_.size();
+        if (inflate_on_device(first, end, total ? &b.data[0] : nullptr, total)) {
+            dev_members_ += cnt;
+            return;
+        }
+        host_members_ += cnt;
         // bad: the lowest index (within the batch) of a member that failed, with how far zlib got
         // in it; each thread stops at its own first failure, enough since its later members could
         // only raise it
@@ -534,6 +610,13 @@ class BgzfSource {
     bool bad_ = false;          // ... because the stream is corrupt at limit_
     bool reported_ = false;     // read() has returned false for it
     std::future<Batch> ahead_;  // the next batch, inflating while the queued ones are read
+    // device inflate (used by the one thread that runs inflate_batch at a time)
+    std::string path_;
+    bool device_fits_ = true;      // no member above FQ_INFLATE_MAX
+    int device_ = -1;              // the device to inflate on, -1: the host
+    fq_inflate* infl_ = nullptr;
+    std::vector<fq_inflate_member> desc_;
+    size_t dev_members_ = 0, host_members_ = 0;
 };
 
 // ---- whole gzip files through libdeflate ----
@@ -732,11 +815,13 @@ int gz_inflate_threads() {
     return std::max(2, n / 2);
 }
 
+bool is_bgzf_chain(const std::string& path) { return BgzfSource::open(path, 1) != nullptr; }
+
 // ---- FqBulkReader ----
-FqBulkReader::FqBulkReader(const std::string& path, bool phred64, int buf_size)
+FqBulkReader::FqBulkReader(const std::string& path, bool phred64, int buf_size, int gz_device)
     : phred64_(phred64), bsize_((uint64_t)buf_size) {
     if (ends_with(path, ".gz")) {
-        if ((bgzf_ = BgzfSource::open(path, (size_t)bsize_))) return;
+        if ((bgzf_ = BgzfSource::open(path, (size_t)bsize_, gz_device))) return;
         // a single-stream gzip file: chunks inflated on several threads
         if ((pargz_ = ParGzSource::open(path, (size_t)bsize_, gz_inflate_threads()))) return;
         path_ = path;
@@ -1407,9 +1492,10 @@ void FqBulkReader::seek(uint64_t off) {
 }
 
 // ---- PackReader ----
-PackReader::PackReader(const std::string& in1, const std::string& in2, bool interleaved, bool phred64, int buf_size)
-    : r1_(in1, phred64, buf_size), paired_(!in2.empty() || interleaved), interleaved_(interleaved) {
-    if (!in2.empty() && !interleaved) r2_.reset(new FqBulkReader(in2, phred64, buf_size));
+PackReader::PackReader(const std::string& in1, const std::string& in2, bool interleaved, bool phred64, int buf_size,
+                       int gz_device)
+    : r1_(in1, phred64, buf_size, gz_device), paired_(!in2.empty() || interleaved), interleaved_(interleaved) {
+    if (!in2.empty() && !interleaved) r2_.reset(new FqBulkReader(in2, phred64, buf_size, gz_device));
 }
 
 namespace {

@@ -159,10 +159,14 @@ class GzAhead;
 
 // decoding threads of one single-stream gzip input (ParGzSource)
 int gz_inflate_threads();
+// the file is a chain of BGZF members from its first byte to its last (the bulk reader then
+// inflates it member by member; only the headers are looked at here)
+bool is_bgzf_chain(const std::string& path);
 
 class FqBulkReader {
    public:
-    FqBulkReader(const std::string& path, bool phred64, int buf_size = 1 << 20);
+    // gz_device: the device a BGZF input's members may be inflated on (FQ_GZ_IN_DEVICE=1), -1: none
+    FqBulkReader(const std::string& path, bool phred64, int buf_size = 1 << 20, int gz_device = -1);
     ~FqBulkReader();
     FqBulkReader(const FqBulkReader&) = delete;
     FqBulkReader& operator=(const FqBulkReader&) = delete;
@@ -353,7 +357,7 @@ bool pack_text(Pack& pk, Pool* pool, bool merged = false);
 class PackReader {
    public:
     PackReader(const std::string& in1, const std::string& in2, bool interleaved, bool phred64,
-               int buf_size = 1 << 20);
+               int buf_size = 1 << 20, int gz_device = -1);
     bool next(Pack& pk, size_t max_n, Pool* pool = nullptr);
     bool paired() const { return paired_; }
     uint64_t reads_seen() const { return reads_; }

@@ -2354,7 +2354,9 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
         if (text_mode && !o.interleaved && !(raw_env && std::string(raw_env) == "0") && gz_both && G == 1) {
             const std::string files[2] = {o.in1, o.in2};
             for (int m = 0; m < (paired ? 2 : 1); ++m)
-                if ((pre_gz[m] = ParGzSource::open(files[m], (size_t)1 << 20, gz_inflate_threads()))) pre_gz[m]->prefetch();
+                // (a BGZF chain goes through the bulk reader's member inflater, never through this one)
+                if (!is_bgzf_chain(files[m]) && (pre_gz[m] = ParGzSource::open(files[m], (size_t)1 << 20, gz_inflate_threads())))
+                    pre_gz[m]->prefetch();
         }
         // FQ_GZ_DEVICE=1: the engines compress the output text of text / raw packs (BGZF members, -z
         // as the level) when every output those packs feed is .gz; host packs, and engines without
@@ -2384,7 +2386,8 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
             }
         };
         // (owned here, not by the reader thread: packs in flight point into its file mappings)
-        PackReader pr(o.in1, o.in2, o.interleaved, o.phred64);
+        // (BGZF inputs may inflate on the run's first device: FQ_GZ_IN_DEVICE=1)
+        PackReader pr(o.in1, o.in2, o.interleaved, o.phred64, 1 << 20, devices[0]);
         pr.defer_tiles = true;  // the dispatchers fill the planes while the reader parses on
         // GPU-side record indexing (fq_engine_raw_*) for plain files on one engine: the engine's
         // dispatcher drives the raw stream first; the host reader takes over only where it stops

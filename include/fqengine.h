@@ -564,6 +564,59 @@ int fq_deflate_bgzf(fq_deflate* d, const void* text, size_t n, int32_t level,
                     void* out, size_t out_cap, size_t* out_bytes);     /* host pointers, synchronous */
 int fq_engine_set_gz_out(fq_engine* e, int32_t level);                  /* 0 (default): off */
 
+/* ---- device inflate: BGZF input members inflated on the GPU ---------------------------------------
+ * The mirror of device BGZF.  Every BGZF member is an independent raw deflate stream (RFC 1951)
+ * whose compressed size, ISIZE and CRC32 stand in its header and trailer, so the place of its
+ * bytes in the output is known before anything is inflated: one wave64 inflates one member
+ * (stored, fixed and dynamic blocks, any number of them), checks the produced length against
+ * ISIZE and the CRC32 of the produced bytes, and reports per member the first failure it met:
+ *   FQ_INFL_DATA   the payload is no valid deflate stream, or ends before its last block does
+ *   FQ_INFL_LONG   it would inflate to more than isize bytes (the byte past isize is not written)
+ *   FQ_INFL_SHORT  its last block ended after fewer than isize bytes
+ *   FQ_INFL_CRC    length right, CRC32 wrong
+ * The payload may be any bytes at all: reads are bounded by in_len, writes by isize, distances by
+ * the bytes produced so far in the member.  The device is stricter than zlib about
+ * incomplete code-length sets only (of those it takes none but a distance set with no code or with
+ * a single one-bit code; zlib also lets a one-symbol literal/length code through); it never accepts
+ * what zlib rejects, and bytes after the last block's end are ignored as zlib's inflate() ignores them.
+ * fq_inflate_create sizes the handle's device buffers for calls of up to max_in payload bytes,
+ * max_out output bytes and max_members members; the handle owns one non-blocking stream, and one
+ * thread uses it at a time.
+ * fq_inflate_members refuses (FQ_E_INVALID, nothing written, no launch) a member whose in_len or
+ * isize exceeds FQ_INFLATE_MAX or whose payload does not lie within comp[0, comp_bytes), totals
+ * above the handle's limits, and out_cap below the sum of isize.  Otherwise member i's bytes land
+ * at out + isize[0] + ... + isize[i - 1], status and produced are set in every member, and *n_bad
+ * counts the members that are not FQ_INFL_OK (FQ_OK is returned all the same: bad data is a result,
+ * not a failure of the call).
+ * fq_inflate_bgzf walks the member chain of a whole BGZF file image itself (RFC 1952 header with
+ * the 'BC' extra subfield; the members must cover the n bytes exactly, else FQ_E_INVALID), inflates
+ * all members, and sets *out_bytes to the sum of ISIZE and *first_bad to the index of the first
+ * member that is not OK (-1: none; the bytes before that member's range are good). */
+#define FQ_INFLATE_MAX 65536          /* largest in_len and isize the device takes per member */
+enum { FQ_INFL_OK = 0, FQ_INFL_DATA = 1, FQ_INFL_LONG = 2, FQ_INFL_SHORT = 3, FQ_INFL_CRC = 4 };
+typedef struct fq_inflate_member {
+    uint64_t in_off;    /* the member's deflate payload: offset in `comp` ... */
+    uint32_t in_len;    /* ... and length (<= FQ_INFLATE_MAX) */
+    uint32_t isize;     /* bytes it must inflate to (<= FQ_INFLATE_MAX; 0 is legal: the EOF member) */
+    uint32_t crc;       /* CRC32 they must have */
+    uint32_t status;    /* out: FQ_INFL_* (the first failure met) */
+    uint32_t produced;  /* out: bytes written for this member (== isize when OK, <= isize always) */
+    uint32_t pad;
+} fq_inflate_member;
+typedef struct fq_inflate fq_inflate;
+int fq_inflate_create(int device, size_t max_in, size_t max_out, size_t max_members, fq_inflate** out);
+                                      /* FQ_E_NO_DEVICE as fq_deflate_create */
+int fq_inflate_destroy(fq_inflate* h);
+/* host pointers, synchronous; member i's bytes land at out + sum of isize[0..i).
+ * *n_bad = members whose status is not OK; their output ranges hold `produced` bytes, then unspecified bytes */
+int fq_inflate_members(fq_inflate* h, const void* comp, size_t comp_bytes, fq_inflate_member* m, size_t n,
+                       void* out, size_t out_cap, size_t* n_bad);
+/* a whole BGZF chain: walks the headers itself */
+int fq_inflate_bgzf(fq_inflate* h, const void* bgzf, size_t n, void* out, size_t out_cap,
+                    size_t* out_bytes, int64_t* first_bad /* member index, -1: none */);
+/* the inflate kernel's time in the handle's last call (HIP events around the launch), milliseconds */
+double fq_inflate_last_kernel_ms(const fq_inflate* h);
+
 /* Kernel timing of the engine's last process_device call (HIP events on the launch stream),
  * in milliseconds; 0 when unavailable. */
 double fq_engine_last_kernel_ms(const fq_engine* e);
