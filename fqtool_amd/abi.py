@@ -284,6 +284,16 @@ def load_engine(path=ENGINE_LIB):
     lib.fq_kmer_close.argtypes = [vp]
     lib.fq_kmer_count.argtypes = [vp, i32, i32, i32, vp]
     lib.fq_kmer_find.argtypes = [vp, i32, i32, i32, ctypes.c_uint32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    lib.fq_kstat_create.argtypes = [ctypes.c_int, i32, ctypes.POINTER(vp)]
+    lib.fq_kstat_destroy.argtypes = [vp]
+    lib.fq_kstat_reset.argtypes = [vp]
+    lib.fq_kstat_k.argtypes = [vp]
+    lib.fq_kstat_words.argtypes = [vp]
+    lib.fq_kstat_words.restype = ctypes.c_size_t
+    lib.fq_engine_set_kstat.argtypes = [vp, vp]
+    lib.fq_kstat_read.argtypes = [vp, vp, ctypes.c_size_t]
+    lib.fq_kstat_last_kernel_ms.argtypes = [vp]
+    lib.fq_kstat_last_kernel_ms.restype = ctypes.c_double
     lib.fq_deflate_bound.argtypes = [ctypes.c_size_t]
     lib.fq_deflate_bound.restype = ctypes.c_size_t
     lib.fq_deflate_code_lengths.argtypes = [vp, i32, i32, vp]
@@ -312,6 +322,8 @@ ENGINE_SYMBOLS = [
     "fq_deflate_bound", "fq_deflate_code_lengths", "fq_deflate_create", "fq_deflate_destroy", "fq_deflate_bgzf",
     "fq_engine_set_gz_out",
     "fq_inflate_create", "fq_inflate_destroy", "fq_inflate_members", "fq_inflate_bgzf", "fq_inflate_last_kernel_ms",
+    "fq_kstat_create", "fq_kstat_destroy", "fq_kstat_reset", "fq_kstat_k", "fq_kstat_words", "fq_engine_set_kstat",
+    "fq_kstat_read", "fq_kstat_last_kernel_ms",
 ]
 
 
@@ -338,6 +350,8 @@ def load_host(path=HOST_LIB):
     lib.fqh_session_add_acc.argtypes = [vp, vp, ci]
     lib.fqh_session_dup_params.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
     lib.fqh_session_set_dup.argtypes = [vp, vp, vp, vp]
+    lib.fqh_session_kmer_params.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    lib.fqh_session_set_kmer.argtypes = [vp, vp]
     lib.fqh_session_finish.argtypes = [vp]
     lib.fqh_session_finish.restype = vp
     lib.fqh_session_close.argtypes = [vp]
@@ -359,5 +373,6 @@ HOST_SYMBOLS = [
     "fqh_report_json", "fqh_free", "fqh_session_open", "fqh_session_error", "fqh_session_params",
     "fqh_session_next", "fqh_session_consume", "fqh_session_add_acc", "fqh_session_finish",
     "fqh_session_close", "fqh_debug_records", "fqh_session_dup_params", "fqh_session_set_dup",
+    "fqh_session_kmer_params", "fqh_session_set_kmer",
     "fqh_set_kmer_backend", "fqh_pargz_read_all", "fqh_gzread_all", "fqh_gz_drain",
 ]

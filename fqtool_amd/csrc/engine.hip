@@ -113,6 +113,7 @@ struct fq_engine {
     std::deque<int> raw_queued;
     int raw_prev_slot = -1;
     fq_dup* dup = nullptr;    // duplication table fed by every pack (-d)
+    fq_kstat* kstat = nullptr;  // k-mer tables fed by every pack (--kmer)
     // device BGZF (fq_engine_set_gz_out): level 1..9, 0 = off; the compressor's scratch, one per
     // engine (its launches all run on the compute stream, one after another)
     int gz_level = 0;
@@ -359,6 +360,12 @@ static int launch(fq_engine* e, const fq_batch& db, fq_read_result* dres, hipStr
         const int rc = fq_dup_pack(e->dup, db, e->p.paired, order, s);
         if (rc != FQ_OK) return fail(e, rc, std::string("duplication analysis: ") + fq_dup_error(e->dup));
     }
+    if (e->kstat) {  // the pre-filter k-mers, before -c rewrites the planes (src/peprocessor.cpp:276-277)
+        int rc = FQ_OK;
+        if (!dres) rc = fq_kstat_records(e->kstat, (size_t)db.n * (e->p.paired ? 2 : 1), s, &dres);
+        if (rc == FQ_OK) rc = fq_kstat_pre(e->kstat, db, e->p, s);
+        if (rc != FQ_OK) return fail(e, rc, std::string("k-mer statistics: ") + fq_kstat_error(e->kstat));
+    }
     // (index-filtered pairs are handed to the general kernel one by one)
     if (e->fast) {
         // hand-off list: pair / read indices, reserved a tile's worth (<= 64) at a time, at most
@@ -382,6 +389,10 @@ static int launch(fq_engine* e, const fq_batch& db, fq_read_result* dres, hipStr
     if (timed) {
         HIP_TRY(e, hipEventRecord(e->ev1, s));
         e->timed = true;
+    }
+    if (e->kstat) {  // the post-filter k-mers, from the records the kernels above have written
+        const int rc = fq_kstat_post(e->kstat, db, e->p, dres, s);
+        if (rc != FQ_OK) return fail(e, rc, std::string("k-mer statistics: ") + fq_kstat_error(e->kstat));
     }
     return FQ_OK;
 }
@@ -1090,6 +1101,19 @@ int fq_engine_set_dup(fq_engine* e, fq_dup* d) {
     HIP_TRY(e, hipSetDevice(e->device));
     HIP_TRY(e, hipDeviceSynchronize());  // packs in flight finish with the old table
     e->dup = d;
+    return FQ_OK;
+}
+
+int fq_engine_set_kstat(fq_engine* e, fq_kstat* h) {
+    if (!e) return FQ_E_INVALID;
+    if (h) {
+        int dev = -1;
+        if (fq_kstat_device(h, &dev) != FQ_OK || dev != e->device)
+            return fail(e, FQ_E_INVALID, "the k-mer tables are on another device");
+    }
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipDeviceSynchronize());  // packs in flight finish with the old tables
+    e->kstat = h;
     return FQ_OK;
 }
 

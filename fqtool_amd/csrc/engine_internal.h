@@ -39,6 +39,15 @@ hipError_t fq_launch_synth(const fq_batch& b, uint64_t seed, uint64_t first_inde
 int fq_dup_pack(fq_dup* d, const fq_batch& b, int paired, unsigned long long order_base, hipStream_t s);
 const char* fq_dup_error(const fq_dup* d);
 int fq_dup_device(const fq_dup* d, int* device);
+// k-mer statistics of one pack (kstat.hip): the pre pass reads the original planes, so it goes
+// before the main kernels (-c rewrites the planes in place); the post pass reads the records, so
+// it goes after the last kernel that writes them.  fq_kstat_records lends a record buffer of n
+// entries to a pack whose caller wants no records.
+int fq_kstat_pre(fq_kstat* h, const fq_batch& b, const fq_params& p, hipStream_t s);
+int fq_kstat_post(fq_kstat* h, const fq_batch& b, const fq_params& p, const fq_read_result* res, hipStream_t s);
+int fq_kstat_records(fq_kstat* h, size_t n, hipStream_t s, fq_read_result** out);
+const char* fq_kstat_error(const fq_kstat* h);
+int fq_kstat_device(const fq_kstat* h, int* device);
 // FASTQ-text packs (text.hip): tile planes built from the text; output text of the passing records
 hipError_t fq_launch_text_tiles(const char* d_text, const fq_text_rec* d_rec, int n, int stride, uint8_t* seq,
                                 uint8_t* qual, uint16_t* lens, hipStream_t s);

@@ -1166,8 +1166,8 @@ __device__ __forceinline__ int slot_class(int s) { return (0x67431 >> (4 * s)) &
 // N != base) where one side is >= Q30 and the other <= Q14 takes the good side's base
 // (complemented) and quality.  Each correction is applied where the later steps read the read: the
 // lane's code column (read 2's column holds the reverse complement, so the new code is the other
-// column's code as stored), its quality row in HBM (rewritten in place, as the general kernel
-// does), and the whole-read sums that passFilter and the post statistics derive their window sums
+// column's code as stored), its base and quality rows in HBM (rewritten in place, as the general
+// kernel does), and the whole-read sums that passFilter and the post statistics derive their window sums
 // from.  The pre-trimming statistics must see the original read (src/peprocessor.cpp:276-277):
 // the removed-mode Stats pass counts the corrected base, so the removed block gets
 // (original - corrected) at the base's cycle (pre = kept + removed), and the per-read pre Q20/Q30
@@ -1237,6 +1237,10 @@ __device__ inline bool correct_pair_fast(const fq_params& p, uint32_t* col, uint
             // (removed mode), or the pre block's slots A C T G N with the +128 quality bias
             // (pre/post mode: front trimming, UMI)
             const uint32_t fo = mate && !oN ? ocode ^ 2u : ocode, fn = mate && !nN ? ncode ^ 2u : ncode;
+            // the base row in HBM too, as the general kernel does: what runs after this pack's
+            // kernels on the planes (the post-filter k-mer pass) reads the corrected read
+            const_cast<uint8_t*>((mate ? b.seq2 : b.seq1) + roff)[(P >> 4) * (FQ_TILE_READS * FQ_CHUNK) + (P & 15)] =
+                nN ? (uint8_t)'N' : (uint8_t)"ACTG"[fn];
             if (removed) {
                 const int so = oN ? kRNSlot : (int)fo, sn = nN ? kRNSlot : (int)fn;
                 atomicAdd(reinterpret_cast<unsigned long long*>(lds + rem_block + rcell(P, so)), kCount1 | (unsigned long long)xo);

@@ -182,6 +182,20 @@ int fqh_session_set_dup(fqh_session* s, const uint64_t* hist, const uint64_t* gc
     return 0;
 }
 
+// --kmer: the effective k-mer length (0: nothing to count), and the caller's four KmerCount tables
+// of 4^k counters each, [pre-R1 | pre-R2 | post-R1 | post-R2] (added to what was set before)
+int fqh_session_kmer_params(fqh_session* s, int* enabled, int* k) {
+    *enabled = s->o.kmer;
+    *k = s->o.kmer_k();
+    return 0;
+}
+
+int fqh_session_set_kmer(fqh_session* s, const uint64_t* tables) {
+    if (!s->o.kmer_k() || !tables) return -1;
+    s->acc.add_kmer(s->o.kmer_k(), tables);
+    return 0;
+}
+
 int fqh_session_add_acc(fqh_session* s, const uint64_t* acc, int max_cycles) {
     s->acc.add(acc, max_cycles);
     return 0;

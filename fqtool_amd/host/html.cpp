@@ -217,6 +217,59 @@ HNode stats_quality(const Summary& st, const std::string& filtering, const std::
     return sec;
 }
 
+// Stats::reportHtmlKmer / makeKmerTD, src/stats.cpp:550-629
+HNode stats_kmer(const Summary& st, const std::string& filtering, const std::string& read) {
+    const std::string sub = filtering + ": " + read + ": KMER counting";
+    const std::string div = replace_all(replace_all(sub, " ", "_"), ":", "_");
+    HNode sec("div.section_div");
+    HNode title("div.subsection_title");
+    HNode link("a", sub);
+    link.attr("title", "click to hide/show");
+    link.attr("onclick", "showOrHide('" + div + "')");
+    title.add(link);
+    sec.add(title);
+    HNode id("div#" + div);
+    id.add(HNode("div.sub_section_tips", "Darker background means larger counts. The count will be shown on mouse over"));
+    HNode table("table.kmer_table");
+    table.attr("style", "width:680px;");
+    const size_t side = (size_t)1 << st.kmer_k;  // side * side = 4^k cells
+    HNode head("tr");
+    head.add(HNode("td"));
+    for (size_t h = 0; h < side; ++h) {
+        HNode c("td", std::to_string(h + 1));
+        c.attr("style", "color:#333333");
+        head.add(c);
+    }
+    table.add(head);
+    const double mean_bases = (double)(st.bases + 1) / (double)(int)(side * side);
+    size_t n = 0;
+    for (size_t i = 0; i < side; ++i) {
+        HNode row("tr");
+        HNode first("td", std::to_string(i + 1));
+        first.attr("style", "color:#333333");
+        row.add(first);
+        for (size_t j = 0; j < side; ++j, ++n) {
+            const std::string seq = kmer_text(n, st.kmer_k);
+            const double prop = (double)st.kmer[n] / mean_bases;
+            double frac = 0.5;
+            if (prop > 2.0) frac = (prop - 2.0) / 20.0 + 0.5;
+            else if (prop < 0.5) frac = prop;
+            frac = std::max(0.01, std::min(1.0, frac));
+            const int r = (int)((1.0 - frac) * 255);
+            char hex[8];
+            std::snprintf(hex, sizeof hex, "%02x", r);
+            HNode c("td", seq);
+            c.attr("style", std::string("background:#") + hex + hex + hex);
+            c.attr("title", seq + ": " + std::to_string(st.kmer[n]) + "\n" + fstr(prop) + " times as mean value");
+            row.add(c);
+        }
+        table.add(row);
+    }
+    id.add(table);
+    sec.add(id);
+    return sec;
+}
+
 // Stats::reportHtmlContents, src/stats.cpp:716-806
 HNode stats_contents(const Summary& st, const std::string& filtering, const std::string& read) {
     const std::string sub = filtering + ": " + read + ": base contents";
@@ -592,8 +645,11 @@ std::string build_html(const Options& o, const HostAcc& a, const AdapterCounts& 
     pre_sec.add(pre_title);
     HNode pre_div("div#before_filtering");
     pre_div.add(stats_quality(pre1, "Before filtering", "read1")).add(stats_contents(pre1, "Before filtering", "read1"));
-    if (pe)
+    if (pre1.kmer_k) pre_div.add(stats_kmer(pre1, "Before filtering", "read1"));
+    if (pe) {
         pre_div.add(stats_quality(pre2, "Before filtering", "read2")).add(stats_contents(pre2, "Before filtering", "read2"));
+        if (pre2.kmer_k) pre_div.add(stats_kmer(pre2, "Before filtering", "read2"));
+    }
     body.add(pre_sec);
     body.add(pre_div);
     HNode post_sec("div.section_div");
@@ -605,8 +661,11 @@ std::string build_html(const Options& o, const HostAcc& a, const AdapterCounts& 
     post_sec.add(post_title);
     HNode post_div("div#after_filtering");
     post_div.add(stats_quality(post1, "After filtering", "read1")).add(stats_contents(post1, "After filtering", "read1"));
-    if (pe)
+    if (post1.kmer_k) post_div.add(stats_kmer(post1, "After filtering", "read1"));
+    if (pe) {
         post_div.add(stats_quality(post2, "After filtering", "read2")).add(stats_contents(post2, "After filtering", "read2"));
+        if (post2.kmer_k) post_div.add(stats_kmer(post2, "After filtering", "read2"));
+    }
     post_sec.add(post_div);
     body.add(post_sec);
     HNode sw("div#section_div");

@@ -177,11 +177,11 @@ Table make_table(Options& o) {
     range(t.add({"--umi_skip_length"}, Kind::Int, &o.umi_skip, "bases to skip after umi"), 0, 1000).needs = {"-u"};
     t.add({"--umi_drop_comment"}, Kind::Flag, &o.umi_drop_comment, "drop other comment information").needs = {"-u"};
     t.add({"--umi_not_trim"}, Kind::Flag, &o.umi_not_trim, "do not trim reads").needs = {"-u"};
-    // ---- ORA / k-mer (outside scope)
+    // ---- ORA (outside scope) / k-mer
     t.add({"--ora"}, Kind::Flag, &t.dummy_bool, "enable ORA").unsupported = true;
     range(t.add({"--ora_sample"}, Kind::Int, &t.dummy_int, "ORA sampling steps"), 1, 10000).needs = {"--ora"};
-    t.add({"--kmer"}, Kind::Flag, &t.dummy_bool, "enable kmer analysis").unsupported = true;
-    range(t.add({"--kmer_length"}, Kind::Int, &t.dummy_int, "kmer length to analysis"), 4, 16).needs = {"--kmer"};
+    t.add({"--kmer"}, Kind::Flag, &o.kmer, "enable kmer analysis");
+    range(t.add({"--kmer_length"}, Kind::Int, &o.kmer_length, "kmer length to analysis"), 4, 16).needs = {"--kmer"};
     // ---- reporting / system
     t.add({"-J"}, Kind::Str, &o.json_file, "json format report file");
     t.add({"-H"}, Kind::Str, &o.html_file, "html format report file");
@@ -409,6 +409,11 @@ Options parse_cli(int argc, char** argv) {
             throw CliError("option " + t.specs[k].names[0] + " (" + t.specs[k].help +
                                ") is outside the hot path this MI355X build implements; see DESIGN.md",
                            2);
+    if (o.kmer_k() > FQ_KSTAT_MAX_K)
+        throw CliError("--kmer_length " + std::to_string(o.kmer_length) + " is above this build's limit of " +
+                           std::to_string(FQ_KSTAT_MAX_K) + ": the k-mer tables and reports grow as 4^k, and the reference "
+                           "itself crashes at its nominal maximum of 16",
+                       2);
     return o;
 }
 

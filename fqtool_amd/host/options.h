@@ -2,9 +2,8 @@
 //
 // Mirrors the reference's Options tree (src/options.h:15-386), its CLI (src/main.cpp:18-120,
 // CLI11 1.7.1 semantics: bool flags reset to false at registration, range checks, needs /
-// excludes), and Options::update / validate (src/options.cpp:24-71).  ORA and k-mer analysis
-// (outside this build's scope) are parsed and rejected with a clear message instead of being
-// silently ignored.
+// excludes), and Options::update / validate (src/options.cpp:24-71).  ORA (outside this build's
+// scope) is parsed and rejected with a clear message instead of being silently ignored.
 #pragma once
 
 #include <cstdint>
@@ -66,6 +65,10 @@ struct Options {
     int split_number = 0, digits = 4;
     size_t split_size = 0;
     int est_reads_num = 0;  // Evaluator::evaluateReadNum
+    // --kmer / --kmer_length: the reference's kmer.kmerLen defaults to 0, so --kmer alone counts nothing
+    bool kmer = false;
+    int kmer_length = 0;
+    int kmer_k() const { return kmer ? kmer_length : 0; }  // the effective length (Stats::mKmerLen)
     bool split() const { return split_by_number || split_by_lines; }
     // leading bases UmiProcessor::process trims from mate m (before clamping to the read length)
     int umi_front(int m) const {

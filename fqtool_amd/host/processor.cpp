@@ -31,6 +31,13 @@
 // the test builds) links all the same, and the tool then compresses on the host as before.
 #pragma weak fq_engine_set_gz_out
 #pragma weak fq_deflate_bound
+// The k-mer statistics (--kmer --kmer_length) are bound weakly too; without them such a run fails
+// with a message instead of leaving the KmerCount sections out.
+#pragma weak fq_kstat_create
+#pragma weak fq_kstat_destroy
+#pragma weak fq_kstat_words
+#pragma weak fq_kstat_read
+#pragma weak fq_engine_set_kstat
 
 namespace fqhost {
 namespace {
@@ -1373,10 +1380,12 @@ struct Lane {
         if (t.joinable()) t.join();
         if (e) fq_engine_destroy(e);
         if (dup) fq_dup_destroy(dup);
+        if (kstat) fq_kstat_destroy(kstat);
     }
     int dev, depth;
     fq_engine* e = nullptr;
     fq_dup* dup = nullptr;  // -d: this engine's table, kept across re-creation
+    fq_kstat* kstat = nullptr;  // --kmer: this engine's k-mer tables, kept likewise
     int gz_level = 0;       // FQ_GZ_DEVICE=1 with .gz outputs: text / raw packs come back as BGZF members
     // an output buffer of x bytes of text, sized for its members instead
     size_t out_cap(size_t x) const { return gz_level ? fq_deflate_bound(x) : x; }
@@ -1400,6 +1409,15 @@ struct Lane {
                 throw std::runtime_error("fq_dup_create (device " + std::to_string(dev) + ") failed");
             if (fq_engine_set_dup(e, dup) != FQ_OK)
                 throw std::runtime_error(std::string("fq_engine_set_dup: ") + fq_engine_last_error(e));
+        }
+        if (o.kmer_k()) {
+            if (!fq_kstat_create || !fq_kstat_destroy || !fq_kstat_words || !fq_kstat_read || !fq_engine_set_kstat)
+                throw std::runtime_error("--kmer --kmer_length: this engine library has no k-mer statistics (fq_kstat_*)");
+            if (!kstat && fq_kstat_create(dev, o.kmer_k(), &kstat) != FQ_OK)
+                throw std::runtime_error("fq_kstat_create (device " + std::to_string(dev) + ", k = " +
+                                         std::to_string(o.kmer_k()) + ") failed");
+            if (fq_engine_set_kstat(e, kstat) != FQ_OK)
+                throw std::runtime_error(std::string("fq_engine_set_kstat: ") + fq_engine_last_error(e));
         }
         if (gz_level && fq_engine_set_gz_out(e, gz_level) != FQ_OK)
             throw std::runtime_error(std::string("fq_engine_set_gz_out: ") + fq_engine_last_error(e));
@@ -2605,6 +2623,15 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
             if (fq_dup_stat(lanes[0]->dup, o.dup_hist_size, hist.data(), gcs.data(), tot) != FQ_OK)
                 throw std::runtime_error("fq_dup_stat failed");
             acc.set_dup(hist, gcs, tot[0], tot[1]);
+        }
+        if (o.kmer_k()) {  // every engine's KmerCount tables, added up (the counters are sums)
+            std::vector<uint64_t> buf;
+            for (auto& l : lanes) {
+                if (!l->kstat) continue;
+                buf.resize(fq_kstat_words(l->kstat));
+                if (fq_kstat_read(l->kstat, buf.data(), buf.size()) != FQ_OK) throw std::runtime_error("fq_kstat_read failed");
+                acc.add_kmer(o.kmer_k(), buf.data());
+            }
         }
         outs.close();
         double detect_s = 0;

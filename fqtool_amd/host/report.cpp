@@ -197,9 +197,11 @@ AdapterCounts::Report AdapterCounts::report(int m) const {
     return r;
 }
 
-namespace {
-
-}  // namespace
+std::string kmer_text(size_t key, int k) {
+    std::string s((size_t)k, 'N');
+    for (int i = 0; i < k; ++i, key >>= 2) s[(size_t)(k - i - 1)] = "ATCG"[key & 3];
+    return s;
+}
 
 Summary summarize(const HostAcc& a, int k) {
     Summary s;
@@ -271,6 +273,13 @@ Summary summarize(const HostAcc& a, int k) {
     s.json["TotalCycles"] = Json::i(s.cycles);
     s.json["QualityCurves"] = qc;
     s.json["ContentCurves"] = cc;
+    if (a.kmer_k) {  // src/stats.cpp:411-418: the counts as strings, keyed by the k-mer's text
+        s.kmer_k = a.kmer_k;
+        s.kmer = a.kmer_table(k);
+        Json km = Json::object();
+        for (size_t i = 0; i < (size_t)1 << (2 * s.kmer_k); ++i) km[kmer_text(i, s.kmer_k)] = Json::s(std::to_string(s.kmer[i]));
+        s.json["KmerCount"] = km;
+    }
     return s;
 }
 

@@ -43,6 +43,17 @@ class HostAcc {
     }
     std::vector<uint64_t> dup_hist, dup_gc_sum;
     uint64_t dup_total = 0, dup_dups = 0;
+    // --kmer: the four KmerCount tables of 4^k counters each, [pre-R1 | pre-R2 | post-R1 | post-R2]
+    // (include/fqengine.h fq_kstat_read); tables of several engines add up element-wise
+    void add_kmer(int k, const uint64_t* tables) {
+        const size_t words = (size_t)4 << (2 * k);
+        if (kmer_k != k) kmer.assign(words, 0);
+        kmer_k = k;
+        for (size_t i = 0; i < words; ++i) kmer[i] += tables[i];
+    }
+    const uint64_t* kmer_table(int stats_block) const { return kmer.data() + ((size_t)stats_block << (2 * kmer_k)); }
+    int kmer_k = 0;  // 0: no k-mer counting
+    std::vector<uint64_t> kmer;
 
    private:
     int ism_;
@@ -82,6 +93,9 @@ class AdapterCounts {
     std::vector<std::unique_ptr<Shard>> shards_[2];
 };
 
+// Evaluator::int2seq (src/evaluator.cpp:51-61): a k-mer key as text, A0 T1 C2 G3, first base most significant
+std::string kmer_text(size_t key, int k);
+
 // Stats::summarize + reportJson for accumulator stats block k (src/stats.cpp:147-228, :392-430)
 struct Summary {
     uint64_t reads = 0, bases = 0, q20 = 0, q30 = 0, gc = 0, length_sum = 0;
@@ -89,6 +103,8 @@ struct Summary {
     uint64_t base_contents[8] = {};           // mBaseContents
     std::vector<double> qual_curves[5];       // A, T, C, G, Mean
     std::vector<double> content_curves[6];    // A, T, C, G, N, GC
+    int kmer_k = 0;                           // mKmerLen (0: none)
+    const uint64_t* kmer = nullptr;           // mKmer: 4^k counts (points into the HostAcc)
     Json json;
     int mean_length() const { return reads ? (int)(length_sum / reads) : 0; }
 };

@@ -526,6 +526,35 @@ int fq_kmer_count(fq_kmer_set* s, int32_t keylen, int32_t first, int32_t shift_t
 int fq_kmer_find(fq_kmer_set* s, int32_t keylen, int32_t first, int32_t shift_tail, uint32_t seed, uint64_t* occ,
                  size_t cap, size_t* n_out);
 
+/* ---- k-mer statistics (--kmer --kmer_length k) ------------------------------------------------
+ * The KmerCount tables of the four Stats objects (Stats::statRead, reference src/stats.cpp:245,
+ * 266-274): every window of k consecutive bytes that are all upper-case A/T/C/G is one k-mer, key
+ * = 2-bit codes A0 T1 C2 G3, first base most significant (Evaluator::seq2int); a read shorter than
+ * k has none.  A handle lives on one device and outlives engines, as a duplication table does; an
+ * engine with a handle attached counts every later pack on its compute stream, through every entry
+ * point: the original reads (before the UMI trim and -c, index-filtered pairs included) into the
+ * pre tables, before the pack's main kernels, and after them the reads that reach the post-filter
+ * statRead -- original[start, start + len) of passing reads as -c left them, or with -m the
+ * merged read (its k-mers span the junction) in post-R1 -- into the post tables.  The handle holds
+ * four tables of 4^k uint64 counters, [pre-R1 | pre-R2 | post-R1 | post-R2] (512 MiB at k = 12);
+ * they are sums, so the tables of several engines combine by element-wise addition.  Nothing else
+ * changes: records and accumulators are the same with and without a handle.  A process_device pack
+ * without device_results keeps its records in a buffer of the handle.
+ * fq_kstat_create refuses (FQ_E_INVALID) k outside FQ_KSTAT_MIN_K..FQ_KSTAT_MAX_K: the tables and
+ * the reports grow as 4^k (the reference itself crashes at its nominal maximum of 16).
+ * fq_kstat_last_kernel_ms: device-event time of the last pack's two k-mer passes, milliseconds. */
+#define FQ_KSTAT_MIN_K 4
+#define FQ_KSTAT_MAX_K 12
+typedef struct fq_kstat fq_kstat;
+int fq_kstat_create(int device, int32_t k, fq_kstat** out);
+int fq_kstat_destroy(fq_kstat* h);
+int fq_kstat_reset(fq_kstat* h);                 /* waits for the device, then zeroes the tables */
+int fq_kstat_k(const fq_kstat* h);
+size_t fq_kstat_words(const fq_kstat* h);        /* 4 * 4^k */
+int fq_engine_set_kstat(fq_engine* e, fq_kstat* h); /* NULL detaches; h must be on the engine's device */
+int fq_kstat_read(fq_kstat* h, uint64_t* host, size_t words); /* waits for the device, then copies */
+double fq_kstat_last_kernel_ms(const fq_kstat* h);
+
 /* ---- device BGZF: output text compressed on the GPU ---------------------------------------------
  * A span of text in device memory is cut into members of FQ_BGZF_IN input bytes (the last one
  * shorter; no bytes, no member).  Each member is a complete BGZF member laid out as the host

@@ -56,6 +56,12 @@ int fqh_session_consume(fqh_session* s, const fq_read_result* res, int max_cycle
  * (hist_size bins, GC sums, totals = {reads counted, duplicates}) before fqh_session_finish */
 int fqh_session_dup_params(fqh_session* s, int* enabled, int* keylen, int* hist_size);
 int fqh_session_set_dup(fqh_session* s, const uint64_t* hist, const uint64_t* gc_sum, const uint64_t* totals);
+/* --kmer: whether the command line enables it and the effective k-mer length (0 without
+ * --kmer_length: nothing is counted and the reports carry no KmerCount); the caller counts
+ * (fq_kstat_* on the engine's device) and hands back the four tables of 4^k counters each,
+ * [pre-R1 | pre-R2 | post-R1 | post-R2], before fqh_session_finish (several calls add up) */
+int fqh_session_kmer_params(fqh_session* s, int* enabled, int* k);
+int fqh_session_set_kmer(fqh_session* s, const uint64_t* tables);
 /* adds an accumulator block (fq_engine_read_acc layout at max_cycles) */
 int fqh_session_add_acc(fqh_session* s, const uint64_t* acc, int max_cycles);
 /* closes the outputs, writes the JSON report file (-J) and returns its text (malloc'd, fqh_free) */
