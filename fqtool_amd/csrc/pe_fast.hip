@@ -1,13 +1,16 @@
 // pe_fast.hip -- hot path for paired-end and single-end packs on gfx950 (incl. -m merge).
 //
-// Mapping: one workgroup = 8 waves, one wave = a tile of 32 pairs, one LANE = one READ
-// (lanes 0-31 read 1, lanes 32-63 read 2 of the same pairs), so every per-read operation of
-// PairEndProcessor::processPairEnd (reference src/peprocessor.cpp:261-508) keeps all 64 lanes
-// busy and the two mates of a pair are lanes l and l^32 of the same wave.
+// Mapping: one wave = a tile of 32 pairs, one LANE = one READ (lanes 0-31 read 1, lanes 32-63
+// read 2 of the same pairs), so every per-read operation of PairEndProcessor::processPairEnd
+// (reference src/peprocessor.cpp:261-508) keeps all 64 lanes busy and the two mates of a pair are
+// lanes l and l^32 of the same wave.
 //
-// Occupancy: 16 waves per CU (2 workgroups of 8, the merge variant 1 of 16); the only per-wave
-// LDS is the 2-bit code / N-mask column block (5 KB), and a workgroup's Stats histograms are
-// shared by its waves.
+// Occupancy: 16 waves per CU (one workgroup of 16; LEAN single-end two of 8; see Layout); the
+// per-wave LDS is the 2-bit code / N-mask column block (5 KB) and the prefix-count words, and a
+// workgroup's Stats histograms are shared by its waves.
+//
+// The tuning rounds' rejected variants (A/B switches) are not kept here: DESIGN.md describes them
+// and profiles/ holds their measurements.
 //
 // Staging: each lane streams its seq and qual rows from HBM with 16-byte loads (the batch's
 // chunk-interleaved tiles make each wave-wide chunk load contiguous).  Sequence bytes
@@ -48,148 +51,21 @@ namespace long320 {  // (kernel names tell the two builds apart in profiles)
 namespace {
 #endif
 
-#ifndef FQ_MERGE_ROTATE  // merged-part Stats walk rotated per lane (conflict-free LDS banks; slower)
-#define FQ_MERGE_ROTATE 0
-#endif
-#ifndef FQ_ABLATE_STAGE
-#define FQ_ABLATE_STAGE 0
-#endif
-#ifndef FQ_OPAQUE_NCH
-#define FQ_OPAQUE_NCH 1
-#endif
-#ifndef FQ_OPAQUE_LK
-#define FQ_OPAQUE_LK 1
-#endif
-#ifndef FQ_SCHED_PIN
-#define FQ_SCHED_PIN 1
-#endif
-#ifndef FQ_MERGE_WAVES
-#define FQ_MERGE_WAVES 16  // merge variant: one workgroup of 16 waves per CU (8: 10.8, 12: 9.4, 16: 9.0 ms per 20 M pairs)
-#endif
-#ifndef FQ_MERGE_BLOCKS
-#define FQ_MERGE_BLOCKS 1
-#endif
-#ifndef FQ_LEAN_DIRECT
-#define FQ_LEAN_DIRECT 1  // LEAN passFilter: a window shorter than half the read is summed directly
-#endif
-#ifndef FQ_LEAN_WAVES
-#define FQ_LEAN_WAVES 8  // profiling: waves per workgroup of the LEAN variant
-#endif
-#ifndef FQ_LEAN_BLOCKS
-#define FQ_LEAN_BLOCKS 2  // profiling: workgroups per CU of the LEAN variant
-#endif
-#ifndef FQ_MERGE_QLDS
-#define FQ_MERGE_QLDS 0
-#endif
-#ifndef FQ_AHEAD
-#define FQ_AHEAD 4  // (A/B at 20 M pairs: 3 -> 4 is -1 to -2 % on C3-C5; 5 and 6 are slower)
-#endif
-#ifndef FQ_NFOLD
-#define FQ_NFOLD 1  // removed-mode Stats: N bases by a nibble add (0: the per-N fix-up loop, profiling)
-#endif
-#ifndef FQ_SCAL_PAD
-#define FQ_SCAL_PAD 1  // per-read scalar copies 17 u64 apart: one LDS bank pair per copy (0: 16, profiling)
-#endif
-#ifndef FQ_STATS_PRIO
-#define FQ_STATS_PRIO 3  // s_setprio during the Stats passes (see FQ_PRIO_TRIM)
-#endif
-#ifndef FQ_STATS_PRIO_ALL
-#define FQ_STATS_PRIO_ALL 2  // (with FQ_STATS_PRIO) 1: up to the end of the merged part's Stats; 2: on to the end of the tile (C3 -1 %)
-#endif
-#ifndef FQ_PRIO_TRIM
-#define FQ_PRIO_TRIM 1  // s_setprio after staging (trimAndCut)
-// Issue priority rising with a wave's progress through its tile: staging 0, trimAndCut and polyG 1,
-// overlap to passFilter 2, Stats 3 -- the waves nearest the end of their tile issue first, so the
-// 16 waves of a CU spread over the phases and the memory / LDS work of the late phases (the Stats
+// staging: row chunks requested this many chunks ahead of their use (A/B at 20 M pairs: 3 -> 4 is
+// -1 to -2 % on C3-C5; 5 and 6 are slower)
+constexpr int kAhead = 4;
+// Issue priority (s_setprio) rising with a wave's progress through its tile: staging 0, trimAndCut and
+// polyG 1, overlap to passFilter 2, Stats 3 -- the waves nearest the end of their tile issue first, so
+// the 16 waves of a CU spread over the phases and the memory / LDS work of the late phases (the Stats
 // pass's quality re-reads and atomics) overlaps the VALU of the early ones.  C3 -10 %, C4 -13 %,
-// C5 -10 %, C2 -3 % against staging-only priority (profiles/r05_ab_prio_*.txt).
-#endif
-#ifndef FQ_PRIO_POLYG
-#define FQ_PRIO_POLYG 1  // s_setprio from polyG on
-#endif
-#ifndef FQ_PRIO_OV
-#define FQ_PRIO_OV 2  // from the overlap analysis on
-#endif
-#ifndef FQ_PRIO_FILTER
-#define FQ_PRIO_FILTER 2  // from passFilter on
-#endif
-#ifndef FQ_STAGE_PRIO
-#define FQ_STAGE_PRIO 0  // s_setprio during staging (round 4: 1, -2 % against none; with the later phases above it, 0)
-#endif
-#ifndef FQ_DESYNC
-#define FQ_DESYNC 0  // profiling: initial s_sleep stagger of co-resident waves
-#endif
-#ifndef FQ_CUT_W4
-#define FQ_CUT_W4 1  // cut_right windows <= 4 decided per low chunk (0: the word-stream scan, profiling)
-#endif
-#ifndef FQ_FILTER_BATCH
-#define FQ_FILTER_BATCH 1  // passFilter's trimmed / direct ranges: row chunks loaded four at a time
-#endif
-#ifndef FQ_STATS_AHEAD
-#define FQ_STATS_AHEAD 2  // removed-mode Stats: quality chunks requested this many chunks ahead
-#endif
-#ifndef FQ_VK
-#define FQ_VK 1  // staging: the SWAR masks and limits as VGPR values (a VALU op with an SGPR operand issues at half rate)
-#endif
-#ifndef FQ_EXO3
-#define FQ_EXO3 1  // staging: exotic bytes OR-accumulated with one v_bitop3 (full rate) instead of v_sad_u8
-#endif
-#ifndef FQ_STG2
-#define FQ_STG2 1  // staging: the chunk's code and N-flag words from two nibble-packed key words
-#endif
-#ifndef FQ_PG4
-#define FQ_PG4 1  // polyG: the all-G groups at the scan's start (a G tail) passed over by a light loop
-#endif
-#ifndef FQ_PG3
-#define FQ_PG3 1  // polyG: the scan loop loads group g+1's column words before deciding group g
-#endif
-#ifndef FQ_PG2
-#define FQ_PG2 1  // polyG: group 0 decided without the loop when the break is the second non-G base
-#endif
-#ifndef FQ_PREFIX
-#define FQ_PREFIX 1  // LEAN: per-chunk prefix counts staged in LDS, passFilter reads them (0: the trimmed-tail loop)
-#endif
-#ifndef FQ_PLAUNDER
-#define FQ_PLAUNDER 1  // re-read fq_params / fq_batch from the kernarg segment every tile (SGPR pressure)
-#endif
-#ifndef FQ_ST_SH64
-#define FQ_ST_SH64 1  // removed-mode Stats: slot nibbles positioned two at a time by 64-bit shifts
-#endif
-#ifndef FQ_ST_KM2
-#define FQ_ST_KM2 1  // removed-mode Stats: kept mask by one med3 + one bitop3 per word, 64-bit spread
-#endif
-#ifndef FQ_ST_PF2
-#define FQ_ST_PF2 1  // removed-mode Stats: column words requested two chunks ahead (no wait on the atomics)
-#endif
-#ifndef FQ_OVX2
-#define FQ_OVX2 1  // overlap exact check: word pairs by ds_read2st64 + 64-bit shifts, the 50-position test peeled
-#endif
-#ifndef FQ_MRG2
-#define FQ_MRG2 1  // merged-part Stats: groups unrolled (immediate row offsets), qualities through a tile buffer
-#endif
-#ifndef FQ_ADSEQ_LDSBITS
-#define FQ_ADSEQ_LDSBITS 0  // adseq_search's candidate scan: the adapter's bit words from LDS (FixedLds) instead of v_bfe
-#endif
-#ifndef FQ_OV_SH64
-#define FQ_OV_SH64 1  // overlap candidates: planes realigned by 64-bit shifts (one block per pass)
-#endif
-#ifndef FQ_OV12
-#define FQ_OV12 0  // overlap candidates at the default limit 5 from the first 12 positions (not 16): slower (a false candidate in any lane costs the wave an exact check; profiles/r05_ab_ov12_stvcc.txt)
-#endif
-#ifndef FQ_OV_CSHIFT
-#define FQ_OV_CSHIFT 1  // overlap candidates: the block words through a shift register (not a select per word on the runtime block index)
-#endif
-#ifndef FQ_FASTMASK
-#define FQ_FASTMASK 1  // posmask at the hot sites and staging's partial-chunk byte masks by v_med3 + 64-bit shifts (neutral to -0.5 %, profiles/r05_ab_fastmask_runshift.txt)
-#endif
-#ifndef FQ_ST_VCC
-#define FQ_ST_VCC 0  // removed-mode Stats: the rotation selects as VCC-masked v_cndmask_e32 (no gain measured, profiles/r05_ab_ov12_stvcc.txt)
-#endif
-#ifndef FQ_PREFETCH
-#define FQ_PREFETCH 0  // profiling: after staging, pull the first FQ_PREFETCH chunks of the wave's next tile
-                       // toward L2 with LDS-DMA loads (0: off; measured slower at 10)
-#endif
-constexpr int kAhead = FQ_AHEAD;  // staging: row chunks requested this many chunks ahead of their use
+// C5 -10 %, C2 -3 % against staging-only priority (profiles/r05_ab_prio_*.txt).  The Stats priority
+// holds to the end of the tile: the next tile's staging resets it (C3 -1 % against a reset after Stats).
+constexpr int kPrioStage = 0;   // (round 4: 1, -2 % against none; with the later phases above it, 0)
+constexpr int kPrioTrim = 1;    // after staging: trimAndCut
+constexpr int kPrioPolyG = 1;   // from polyG on
+constexpr int kPrioOv = 2;      // from the overlap analysis on
+constexpr int kPrioFilter = 2;  // from passFilter on
+constexpr int kPrioStats = 3;   // the Stats passes
 constexpr int kBlock = 1024;  // largest workgroup (the launch bound of each variant is its own size)
 #ifndef FQ_MAXLEN
 #define FQ_MAXLEN 160  // pe_fast_long.hip builds this file again for reads up to 320 bp
@@ -201,7 +77,6 @@ constexpr int kChunks = kMaxLen / 16;             // 16-position chunks per read
 constexpr int kFC = 0;                            // column fields (words): 2-bit codes,
 constexpr int kFN = kChunks;                      //   spaced N mask (+ lowercase flags at the odd bits),
 constexpr int kCodeW = 2 * kChunks * 64;          // code + N columns of a wave
-constexpr int kQS = kMaxLen / 4 + 1;              // quality row stride (odd: conflict-free per lane)
 // Stats histograms: u64 cells [cycle / 16][slot][cycle % 16], slots A C T G N + one dummy slot
 // that absorbs masked-off positions.  A cell's LDS bank pair depends only on cycle % 16, so the
 // 16 lanes of an atomic's lane group (distinct cycle % 16 by the per-lane rotation) never
@@ -225,8 +100,6 @@ constexpr int cmax(int a, int b) { return a > b ? a : b; }
 constexpr int kSmallU64 = FQ_ACC_INSERT;                 // FilterResult / adapter / polyX / merged counters
 constexpr int kSmallW = 2 * ((kSmallU64 + 1) & ~1);
 constexpr int kInsW = (512 + 1 + 1) & ~1;                 // insert-size histogram, u32 per workgroup
-// per-read scalars are spread over kScalCopies LDS copies (lane % copies), each
-// [4 stats][reads, length_sum, q20, q30] u64; the merge variant keeps 8 (LDS budget)
 // adseq_search's adapter columns (per mate: 2-bit codes; read 2's reversed and complemented)
 constexpr int kAdCW = 10;    // words of an adapter column (positions < FQ_MAX_ADAPTER, + one look-ahead)
 constexpr int kAdRc = 144;   // read 2's adapter column: index y holds position kAdRc - 1 - y
@@ -236,16 +109,17 @@ static_assert(kAdRc >= FQ_MAX_ADAPTER + 15 && kAdRc + 16 <= 16 * kAdCW && FQ_MAX
 constexpr int kAdWinOff = 2 * FQ_MAX_ADAPTER / 4, kAdColOff = kAdWinOff + 16, kAdBitOff = kAdColOff + 2 * kAdCW;
 constexpr int kAdW = kAdBitOff + 2 * 16 * 2;
 static_assert(kAdBitOff % 2 == 0, "(fh, fl) pairs 8-byte aligned");
-constexpr int kScalStride = FQ_SCAL_PAD ? 17 : 16;  // u64 per scalar copy (17: copies on distinct LDS bank pairs)
-constexpr int kPfW = FQ_PREFETCH ? 64 : 0;             // LDS-DMA prefetch sink (never read)
-// Every variant re-reads qualities from the rows in L2 (no LDS quality rows) and runs 16 waves
-// per CU: LEAN and FULL as 2 workgroups of 8 waves (128 VGPRs), the merge variant, whose Stats
-// blocks are larger (read 2's merged parts land at read 1's post cycles up to 319), as one
-// workgroup of 16 waves.  The long-read build (320-position columns) fits one 8-wave workgroup.
+// per-read scalars are spread over kScalCopies LDS copies (lane % copies), each
+// [4 stats][reads, length_sum, q20, q30] u64, 17 u64 apart (not 16: the copies then sit on distinct
+// LDS bank pairs); the merge variant keeps 8 copies (LDS budget)
+constexpr int kScalStride = 17;
+// Every variant re-reads qualities from the rows in L2 (no LDS quality rows).  The 160-position build
+// runs 16 waves per CU: one workgroup of 16 waves where the prefix counts (kPfx) are staged -- every
+// variant but LEAN single-end, which runs two workgroups of 8.  The merge variant's Stats blocks are
+// larger (read 2's merged parts land at read 1's post cycles up to 319).  The long-read build
+// (320-position columns) fits one 8-wave workgroup, its merge variant one of 4 waves.
 template <bool LEAN, bool MERGE = false, bool PAIRED = true>
 struct Layout {
-    // quality rows staged in LDS (off: rows are re-read from L2); profiling switch for the merge variant
-    static constexpr bool kQLds = MERGE && FQ_MERGE_QLDS;
     // Each lane's running quality / N counts (q20 | q30 << 8 | low << 16 | N << 24) at the end of every
     // kPfxStep-th row chunk, staged in LDS (word kCodeW + (chunk / kPfxStep) * 64 + lane of the wave's
     // block), so passFilter gets a window's counts from prefix words and at most kPfxStep chunks of
@@ -253,16 +127,16 @@ struct Layout {
     // workgroup of 16 waves (whose waves share one histogram) instead of two of 8; the merge variant
     // (already one workgroup, with larger histograms) has room for one word per two chunks.
     // (LEAN single-end, C2, trims nothing; the long build has no room.)
-    static constexpr bool kPfx = FQ_PREFIX && kMaxLen <= 160 && !kQLds && (!LEAN || PAIRED);
+    static constexpr bool kPfx = kMaxLen <= 160 && (!LEAN || PAIRED);
     static constexpr int kPfxStep = MERGE ? 2 : 1;
-    static constexpr int kBlocksPerCU = (kQLds || kMaxLen > 160 || kPfx) ? 1 : MERGE ? FQ_MERGE_BLOCKS : LEAN ? FQ_LEAN_BLOCKS : 2;
-    // (the long build's merge variant: its 320-position columns and 640-cycle merged Stats fit 4 waves)
-    static constexpr int kWaves = MERGE ? (kQLds ? 7 : kMaxLen > 160 ? 4 : FQ_MERGE_WAVES)
-                                        : kPfx ? 16 : (LEAN && kMaxLen <= 160) ? FQ_LEAN_WAVES : 8;
+    static constexpr int kBlocksPerCU = (kMaxLen > 160 || kPfx || MERGE) ? 1 : 2;
+    // (the long build's merge variant: its 320-position columns and 640-cycle merged Stats fit 4 waves;
+    // the merge variant of this build by waves per workgroup: 8: 10.8, 12: 9.4, 16: 9.0 ms per 20 M pairs)
+    static constexpr int kWaves = MERGE ? (kMaxLen > 160 ? 4 : 16) : kPfx ? 16 : 8;
     static constexpr int kWavesPerEU = (kWaves * kBlocksPerCU + 3) / 4;
     static constexpr int kThreads = 64 * kWaves;
     static constexpr int kPfxW = kPfx ? kChunks / kPfxStep * 64 : 0;
-    static constexpr int kWaveW = kCodeW + kPfxW + (kQLds ? 64 * kQS : 0);
+    static constexpr int kWaveW = kCodeW + kPfxW;
     // [pre1, pre2, post1 (x2 with MERGE), post2] (+ MERGE: read 2's merged parts, cycles 0..319,
     // in removed mode, which uses blocks 0-3 as the kept/removed rows of the two mates)
     static constexpr int kHists = MERGE ? 6 : 4;
@@ -277,7 +151,7 @@ struct Layout {
     static constexpr int kScalCopies = MERGE ? 8 : 16;
     static constexpr int kScalW = 2 * kScalStride * kScalCopies;
     static constexpr int kHrW = 2 * kWaves;  // per wave: hand-off list reservation (next slot, slots left)
-    static constexpr int kLdsW = kColsW + kHistRegW + kSmallW + kInsW + kScalW + kAdW + kHrW + kPfW;
+    static constexpr int kLdsW = kColsW + kHistRegW + kSmallW + kInsW + kScalW + kAdW + kHrW;
     static_assert(kLdsW * 4 * kBlocksPerCU <= 160 * 1024, "LDS budget");
     static_assert((kColsW & 1) == 0 && (kHistW & 1) == 0, "u64 cells must stay 8-byte aligned");
     static_assert(kThreads <= kBlock, "launch bound");
@@ -301,9 +175,7 @@ __device__ __forceinline__ uint32_t xor32(uint32_t x) { return (uint32_t)xor32((
 // rematerialise it there): on gfx950 a full-rate VALU op (and, xor, add, bitop3, ...) with an SGPR
 // operand issues at the half rate of the VOP3 ops (profiles/r04_micro_opcost2.txt).
 __device__ __forceinline__ uint32_t vk(uint32_t x) {
-#if FQ_VK
     asm volatile("" : "+v"(x));
-#endif
     return x;
 }
 
@@ -321,22 +193,19 @@ __device__ __forceinline__ uint32_t posmask(int n) {
 }
 // the same at the hot sites of every variant: 2n clamped to [0, 32] by one v_med3, then the low
 // word of ~(~0 << 2n) by one full-rate 64-bit shift (the compare / select form costs two
-// half-rate shifts and two v_cndmask with their wait states)
+// half-rate shifts and two v_cndmask with their wait states; neutral to -0.5 %,
+// profiles/r05_ab_fastmask_runshift.txt)
 __device__ __forceinline__ uint32_t posmask_v(int n) {
-#if FQ_FASTMASK
     int c;
     asm("v_med3_i32 %0, %1, 0, 32" : "=v"(c) : "v"(n + n));
     unsigned long long x;
     asm("v_lshlrev_b64 %0, %1, -1" : "=v"(x) : "v"(c));
     return ~(uint32_t)x & 0x55555555u;
-#else
-    return posmask(n);
-#endif
 }
 
 // byte masks of the first n4 / 4 bytes of a 16-byte chunk, dwords 0-3 (n4 = 4 x bytes, any value):
 // per 8-byte half ~((~0 << c) << c) with c = 4 x its bytes clamped to [0, 32]
-[[maybe_unused]] __device__ __forceinline__ void chunk_bytemask(int n4, uint32_t m[4]) {
+__device__ __forceinline__ void chunk_bytemask(int n4, uint32_t m[4]) {
     int c0, c1;
     asm("v_med3_i32 %0, %1, 0, 32" : "=v"(c0) : "v"(n4));
     asm("v_med3_i32 %0, %1, 0, 32" : "=v"(c1) : "v"(n4 - 32));
@@ -596,7 +465,8 @@ __device__ __forceinline__ void csa(uint32_t& hi, uint32_t& lo, uint32_t a, uint
 // Compared position j's fixed code bits, each as a word of 0s or 1s (fh: high bit, fl: low bit):
 //  * FixedOwn: from the lane's own fixed word (the overlap: a window of the other mate), two v_bfe;
 //  * FixedLds: precomputed in LDS (trimBySequence: the adapter's first 16 codes, the same for every
-//    lane of a mate), one broadcast ds_read_b64 and no VALU.
+//    lane of a mate), one broadcast ds_read_b64 and no VALU.  Measured slower than FixedOwn there and
+//    not instantiated at present; its LDS words are still filled at kernel start (pe_fast_kernel).
 struct FixedOwn {
     uint32_t fu;  // unzip2(fixed)
     __device__ __forceinline__ void next_block() {}
@@ -641,67 +511,32 @@ __device__ inline void ov_candidates(const uint32_t* col, int cm, int mpos, FX f
 #pragma unroll
     for (int k = 2; k < kOvBlocks; ++k)
         if (__any(cnt > 32 * k)) nblk = k + 1;
-#if FQ_OV_CSHIFT
     // the blocks' words enter a shift register at the top, the others moving down one (kOvBlocks - 1
     // moves per block instead of a select per word on the runtime index bk); after the loop they sit
     // kOvBlocks - nblk places too high and move down with zeros
     uint32_t creg[kOvBlocks];
 #pragma unroll
     for (int i = 0; i < kOvBlocks; ++i) creg[i] = 0u;
-#else
-#pragma unroll
-    for (int bk = 0; bk < kOvBlocks; ++bk)
-        if (bk >= nblk) cand[bk] = 0u;
-#endif
 #pragma unroll 1
     for (int bk = 0; bk < nblk; ++bk) {
         fx.next_block();
         if (bk < kOvBlocks - 1) planes(L1, H1);
         else L1 = H1 = 0u;
         // mismatch vector of compared position j over the block's 32 offsets
-#if FQ_OV_SH64
         const unsigned long long HA = (unsigned long long)H1 << 32 | H0, LA = (unsigned long long)L1 << 32 | L0;
         auto shr64 = [](unsigned long long v, int j) -> uint32_t {
             unsigned long long r;
             asm("v_lshrrev_b64 %0, %2, %1" : "=v"(r) : "v"(v), "i"(j));
             return (uint32_t)r;
         };
-#endif
         auto m = [&](int j) -> uint32_t {
-#if FQ_OV_SH64
             const uint32_t hs = j ? shr64(HA, j) : H0;
             const uint32_t ls = j ? shr64(LA, j) : L0;
-#else
-            const uint32_t hs = j ? __builtin_amdgcn_alignbit(H1, H0, j) : H0;
-            const uint32_t ls = j ? __builtin_amdgcn_alignbit(L1, L0, j) : L0;
-#endif
             uint32_t fh, fl;
             fx.bits(j, fh, fl);
             return (hs ^ fh) | (ls ^ fl);
         };
         uint32_t lt;
-#if FQ_OV12
-        if (K == 5) {
-            // the default limit: an accepted offset has < 5 mismatches in its first min(ol, 50)
-            // positions, so in its first 12 (ol >= 16 here) -- a weaker filter than 16 positions
-            // (~0.3 random candidates per 120 offsets instead of ~0.004, each one exact check) at
-            // three quarters of the cost
-            uint32_t ones = 0u, twos = 0u, fours = 0u, twosA, twosB, foursA, foursB, eightsA;
-            csa(twosA, ones, ones, m(0), m(1));
-            csa(twosB, ones, ones, m(2), m(3));
-            csa(foursA, twos, twos, twosA, twosB);
-            csa(twosA, ones, ones, m(4), m(5));
-            csa(twosB, ones, ones, m(6), m(7));
-            csa(foursB, twos, twos, twosA, twosB);
-            csa(eightsA, fours, fours, foursA, foursB);
-            csa(twosA, ones, ones, m(8), m(9));
-            csa(twosB, ones, ones, m(10), m(11));
-            csa(foursA, twos, twos, twosA, twosB);
-            // count = ones + 2 twos + 4 (fours + foursA) + 8 eightsA < 5
-            lt = ~(eightsA | (fours & foursA) | ((fours | foursA) & (twos | ones)));
-        } else
-#endif
-        {
         // 16 vectors -> bit-sliced 5-bit counts, Harley-Seal carry-save order (few live values)
         uint32_t ones = 0u, twos = 0u, fours = 0u, eights = 0u, sixteen, twosA, twosB, foursA, foursB, eightsA, eightsB;
         csa(twosA, ones, ones, m(0), m(1));
@@ -736,9 +571,7 @@ __device__ inline void ov_candidates(const uint32_t* col, int cm, int mpos, FX f
             }
             if (K > 31) lt = ~0u;
         }
-        }
         const int nb = cnt - 32 * bk;  // valid offsets of this block
-#if FQ_OV_CSHIFT
         // bits [0, nb), nb clamped to [0, 32]: the low word of ~(~0 << nb) by one 64-bit shift
         int nbc;
         asm("v_med3_i32 %0, %1, 0, 32" : "=v"(nbc) : "v"(nb));
@@ -747,13 +580,9 @@ __device__ inline void ov_candidates(const uint32_t* col, int cm, int mpos, FX f
 #pragma unroll
         for (int i = 0; i + 1 < kOvBlocks; ++i) creg[i] = creg[i + 1];
         creg[kOvBlocks - 1] = lt & ~(uint32_t)nbx;
-#else
-        cand[bk] = lt & (nb >= 32 ? ~0u : nb <= 0 ? 0u : ((1u << nb) - 1u));
-#endif
         L0 = L1;
         H0 = H1;
     }
-#if FQ_OV_CSHIFT
 #pragma unroll 1
     for (int s = nblk; s < kOvBlocks; ++s) {
 #pragma unroll
@@ -762,7 +591,6 @@ __device__ inline void ov_candidates(const uint32_t* col, int cm, int mpos, FX f
     }
 #pragma unroll
     for (int i = 0; i < kOvBlocks; ++i) cand[i] = creg[i];
-#endif
 }
 
 // AdapterTrimmer::trimBySequence (src/adaptertrimmer.cpp:29-90): the first pos in [start, n - 4)
@@ -776,8 +604,8 @@ __device__ inline void ov_candidates(const uint32_t* col, int cm, int mpos, FX f
 // the kernel start sets adw[5], the window words, the adapter column and its bit words (see
 // pe_fast_kernel).
 //  * pos in [0, n - 16]: full 16-position windows, all at once (ov_candidates; bound < alen/8 + 1,
-//    a superset of every pos's own allowance).  The adapter's bits per compared position are the
-//    same for every lane of a mate, so they come from LDS (FixedLds) instead of two v_bfe a position;
+//    a superset of every pos's own allowance), the adapter's bits per compared position by two v_bfe
+//    from the window word (FixedOwn; adf, the LDS address of FixedLds's words, is not used);
 //  * pos in -4..-1 and [n - 15, n - 5]: one masked window each against that pos's allowance.
 // The survivors' test is the reference's byte comparison restated on the columns, 16 positions a
 // step: with an upper-case ACGT adapter a read byte differs from the adapter byte iff its code
@@ -826,11 +654,7 @@ __device__ inline bool adseq_search(const uint32_t* col, int c, bool rc, int st,
     }
     if (n >= 16) {
         uint32_t cand[kOvBlocks];
-#if FQ_ADSEQ_LDSBITS
-        ov_candidates(col, c, rc ? kMaxLen - st - n : st, FixedLds{adf}, alen / 8 + 1, n - 15, cand);
-#else
         ov_candidates(col, c, rc ? kMaxLen - st - n : st, FixedOwn{unzip2(adw[0])}, alen / 8 + 1, n - 15, cand);
-#endif
         for (;;) {  // candidates in pos order: read 1 from the lowest offset, read 2 from the highest
             int k = -1;
             if (!rc) {
@@ -905,7 +729,6 @@ __device__ inline int polyg_bits(const uint32_t* col, int c, bool rc, int st, in
             return x;
         };
         uint32_t xg = nong(0);  // group g's non-G mask (group 0 first; later groups loaded one ahead)
-#if FQ_PG2
         // Group 0 decides almost every read: while the allowance is 1 (scan indices < 2 per - 1) the
         // scan breaks at the second non-G base; the loop below runs only for the reads it leaves open
         // (a polyG tail, or per < 8).
@@ -918,27 +741,20 @@ __device__ inline int polyg_bits(const uint32_t* col, int c, bool rc, int st, in
                 if (gm) lastG = (31 - __clz(gm)) >> 1;
             }
         }
-#endif
         int g = 0;
-#if FQ_PG4
         // A polyG tail (the reads the shortcut above leaves open): its all-G groups change nothing
         // but firstGpos, so they are passed over at ~16 VALU a group (the loop below spends ~45)
         if (iend == n) {
             while (16 * (g + 1) < n && (xg & posmask_v(n - 16 * g)) == 0u) xg = nong(++g);
             if (g > 0) lastG = 16 * g - 1;  // (scan indices below 16 g are all G)
         }
-#endif
         for (; 16 * g < n && iend == n; ++g) {
             const uint32_t valid = posmask_v(n - 16 * g);
-#if FQ_PG3
             uint32_t x = xg & valid;
             // the next group's column words are requested before this group is decided (a G tail
             // spans several groups, and each LDS round trip otherwise stalls the few lanes that
             // scan -- and with them their wave); past the window they are masked off by `valid`
             xg = nong(g + 1);
-#else
-            uint32_t x = (g ? nong(g) : xg) & valid;
-#endif
             uint32_t gm = ~x & valid;  // G bases of the group
             const int a0 = allowed(16 * g + 1);  // allowance at the group start
             if (cum + __popc(x) > a0) {
@@ -1267,8 +1083,8 @@ __device__ inline bool correct_pair_fast(const fq_params& p, uint32_t* col, uint
     return true;  // (pair-uniform: both lanes walk the same mismatches)
 }
 
-// Per-launch constants derived from fq_params.  With FQ_PLAUNDER the kernel derives them again at the
-// top of every tile from a re-read of the kernarg segment (see the tile loop).
+// Per-launch constants derived from fq_params.  The kernel derives them again at the top of every tile
+// from a re-read of the kernarg segment (see the tile loop).
 #define FQ_DERIVE_PARAMS() \
     [[maybe_unused]] const int abl = p.reserved[0]; \
     [[maybe_unused]] const int nchunks = FIX ? kChunks : min(kChunks, b.stride >> 4); \
@@ -1283,7 +1099,7 @@ __device__ inline bool correct_pair_fast(const fq_params& p, uint32_t* col, uint
     /* UMI in the reads (src/umiprocessor.cpp:10-89, trimFront before trimAndCut): trimAndCut runs on */ \
     /* the read from umi_cut(umi_front, len) on (the general path of trim_and_cut_t) */ \
     [[maybe_unused]] const bool umi = XTRA && (p.umi_front1 > 0 || p.umi_front2 > 0); \
-    [[maybe_unused]] const bool cut_w4 = FQ_CUT_W4 && lowr_ok && !umi && !p.cut_front && !p.cut_tail && p.cut_right_window >= 1 && \
+    [[maybe_unused]] const bool cut_w4 = lowr_ok && !umi && !p.cut_front && !p.cut_tail && p.cut_right_window >= 1 && \
                         p.cut_right_window <= 4; \
     /* Without front trimming every kept window starts at 0, so each base lands in exactly one of */ \
     /* two disjoint blocks: "kept" (inside a passing read's window; the post block) or "removed" */ \
@@ -1308,9 +1124,14 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
     using LY = Layout<LEAN, MERGE, PAIRED>;
     constexpr int kWaves = LY::kWaves, kThreads = LY::kThreads;
     // the paired exact check where it fits the registers (FULL without -m spills with it)
-    constexpr bool kOvx2 = FQ_OVX2 && (LEAN || MERGE);
+    constexpr bool kOvx2 = LEAN || MERGE;
+    // Never set.  It guarded the merge variant's quality rows staged in LDS, a rejected experiment
+    // that no longer fits the LDS budget; its arms in staging's dword() and in qchunk() below are
+    // dead, but they shape those closures' captures, and without them the compiler orders the
+    // staging loads of most instantiations differently.  They go with the next change that
+    // re-times the kernel.
+    constexpr bool kQLds = false;
     uint32_t* col = lds + wave * LY::kWaveW;  // code / N columns: word field*64 + lane
-    uint32_t* qrows = col + kCodeW;           // full variant: quality rows, row = lane
     uint32_t* hist = lds + LY::kColsW;        // [pre1, pre2, post1, post2] x kHistW (post1 x2 with MERGE)
     unsigned long long* small = reinterpret_cast<unsigned long long*>(hist + LY::kHistRegW);
     unsigned int* ins = reinterpret_cast<unsigned int*>(small + kSmallW / 2);
@@ -1354,7 +1175,7 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
         adw[kAdColOff - kAdWinOff + m * kAdCW + w] = v;
     } else if (threadIdx.x >= 64 && threadIdx.x < 64 + 2 * 16) {
         // (fh, fl) of compared position j of each mate's first window (adw[8 m], as ov_candidates'
-        // FixedOwn would derive them)
+        // FixedOwn would derive them), for FixedLds
         const int m = (threadIdx.x - 64) >> 4, j = (threadIdx.x - 64) & 15;
         const uint8_t* a = m ? p.adapter2 : p.adapter1;
         uint32_t w = 0;
@@ -1386,18 +1207,11 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
 #define FQ_STAMP(i)
 #endif
 
-#if FQ_DESYNC
-    {   // profiling: stagger the waves that share a SIMD (wave w, w + 4 of both workgroups of a CU)
-        const int slot = (wave >> 2) + 2 * (blockIdx.x & 1);
-        for (int i = 0; i < slot * FQ_DESYNC; ++i) __builtin_amdgcn_s_sleep(127);
-    }
-#endif
     // hand-off list: a wave reserves kItems slots at a time (its reservation lives in LDS, hres,
     // read only on the rare hand-off path)
     constexpr int kItems = PAIRED ? 32 : 64;
     constexpr int kHole = 0x7FFFFFFF;
     for (int t = blockIdx.x * kWaves + wave; t < ntiles; t += gridDim.x * kWaves) {
-#if FQ_PLAUNDER
         // The parameters and the batch descriptor are re-read from the kernarg segment every tile
         // (scalar loads, cached): kept live across the tile loop they overflow the SGPR file, and the
         // spills cost VALU (v_writelane / v_readlane) and scratch traffic inside the loop.
@@ -1413,7 +1227,6 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
         const fq_params& p = *(const fq_params*)kp_;
         const fq_batch& b = *(const fq_batch*)kb_;
         FQ_DERIVE_PARAMS()
-#endif
         // Per-lane values are derived from an opaque copy of the lane id inside the loop: left to
         // itself the compiler hoists dozens of them out of the tile loop and spills them.
         int lane_x = lane;
@@ -1429,20 +1242,13 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
         uint32_t* my_pre = hist + mate * kHistW;
         uint32_t* my_post = hist + (2 + (MERGE ? 2 : 1) * mate) * kHistW;  // post block, or the "removed" block
         const int r = lane_x & 15;  // stats rotation within a chunk
-        uint32_t* qrow = qrows + lane_x * kQS;
-#ifdef FQ_SAME_TILE  // profiling only: every wave re-reads a few L2-resident tiles (results invalid)
-        const int tt = t & (FQ_SAME_TILE - 1);
-        const int idx = PAIRED ? tt * 32 + pl : tt * 64 + lane_x;
-#else
+        uint32_t* qrow = col + kCodeW + lane_x * (kMaxLen / 4 + 1);  // (kQLds: dead)
         const int idx = PAIRED ? t * 32 + pl : t * 64 + lane_x;
-#endif
         bool valid = idx < b.n;  // (both cleared below for a pair handed to the general kernel)
         int L = valid ? (int)(mate ? b.len2[idx] : b.len1[idx]) : 0;
 
         // ---------------- staging ----------------
-#if FQ_STAGE_PRIO || FQ_STATS_PRIO_ALL == 2
-        __builtin_amdgcn_s_setprio(FQ_STAGE_PRIO);
-#endif
+        __builtin_amdgcn_s_setprio(kPrioStage);
         // chunk-interleaved batch tiles (include/fqengine.h): chunk k of this lane's row is 512 B
         // after chunk k-1, so each chunk load of the wave is one (PE: two planes x 32 rows) or
         // two (SE: 64 rows) 512-byte contiguous runs
@@ -1451,9 +1257,9 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
         const size_t roff = (size_t)(ridx / FQ_TILE_READS) * FQ_TILE_READS * b.stride + (ridx % FQ_TILE_READS) * FQ_CHUNK;
         const uint8_t* S = (mate ? b.seq2 : b.seq1) + roff;
         const uint8_t* Q = (mate ? b.qual2 : b.qual1) + roff;
-        // quality chunk F of this lane's row: from the LDS row (full) or the row in L2 (LEAN)
+        // quality chunk F of this lane's row, re-read from the row (an L2 hit after staging)
         auto qchunk = [&](int F) -> uint4 {
-            if (!LY::kQLds) return *reinterpret_cast<const uint4*>(Q + cst * F);
+            if (!kQLds) return *reinterpret_cast<const uint4*>(Q + cst * F);
             return make_uint4(qrow[4 * F], qrow[4 * F + 1], qrow[4 * F + 2], qrow[4 * F + 3]);
         };
         // (merge: a merged read, at most len1 + len2 long, must fit max_cycles as well)
@@ -1479,9 +1285,7 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
         // opaque per tile: the per-chunk offsets and in-row flags derived from it would otherwise
         // be hoisted out of the tile loop and spilled
         int nch = nchunks;
-#if FQ_OPAQUE_NCH
         if constexpr (!FIX) asm volatile("" : "+s"(nch));
-#endif
         const int lastc = nch - 1;
         uint4 sb[kChunks], qb[kChunks];
 #pragma unroll
@@ -1496,38 +1300,29 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                 sb[k + kAhead] = *reinterpret_cast<const uint4*>(S + cst * min(k + kAhead, lastc));
                 qb[k + kAhead] = *reinterpret_cast<const uint4*>(Q + cst * min(k + kAhead, lastc));
             }
-#if FQ_SCHED_PIN
             // keep the loads where they are: left alone, the scheduler hoists them all to the top
             // of the tile and then waits for every one of them before chunk 0
             __builtin_amdgcn_sched_barrier(0);
-#endif
-#if FQ_ABLATE_STAGE == 1  // profiling only: loads consumed, nothing computed (results invalid)
-            if (k < nch) tqf ^= s4.x ^ s4.y ^ s4.z ^ s4.w ^ q4.x ^ q4.y ^ q4.z ^ q4.w;
-            if (false) {
-#else
             if (k < nch) {
-#endif
                 const uint32_t sw[4] = {s4.x, s4.y, s4.z, s4.w};
                 const uint32_t qw[4] = {q4.x, q4.y, q4.z, q4.w};
                 uint32_t cc = 0, nn4 = 0, lr = 0;
-                uint32_t kkj[4];  // (FQ_STG2) the four dwords' 3-bit keys
+                uint32_t kkj[4];  // the four dwords' 3-bit keys
                 // bases of this chunk still in the read; opaque, or the masks of all ten chunks
                 // (functions of L alone) are computed up front and kept live across the loop
                 int Lk = L - 16 * k;
-#if FQ_OPAQUE_LK
                 asm volatile("" : "+v"(Lk));
-#endif
                 const bool full = __all(Lk >= 16);
                 // per dword: codes, N flags, exotic-byte check and the quality sums; bytes >= 128
                 // send the tile to the general kernel, so q + c (c < 128) never carries into the
                 // next byte for the bytes that count.  FULL: every byte is inside the read (the
                 // common case, no byte masks).
-                uint32_t pbm[4], pbms[4];  // (FQ_FASTMASK: a partial chunk's byte masks, made once)
+                uint32_t pbm[4], pbms[4];  // a partial chunk's byte masks, made once by chunk_bytemask
                 // (not in the full non-merge variants: the eight live masks spill there)
-                constexpr bool kChunkMask = FQ_FASTMASK && (LEAN || MERGE);
+                constexpr bool kChunkMask = LEAN || MERGE;
                 auto dword = [&](int j, auto full_c) {
                     constexpr bool FULL = decltype(full_c)::value;
-                    if (LY::kQLds) qrow[4 * k + j] = qw[j];
+                    if (kQLds) qrow[4 * k + j] = qw[j];
                     const uint32_t bm = FULL ? 0xFFFFFFFFu : kChunkMask ? pbm[j] : bytemask(Lk - 4 * j);
                     // read 2 (the column holds its reverse complement): the chunk's bytes reversed
                     // (dword 3 - j byte-swapped, one v_perm), so its codes come out in column order
@@ -1536,15 +1331,9 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                     const uint32_t kk = (sr >> 1) & 0x07070707u;
                     // canonical byte for the 3-bit key: A C T G (0-3), N (7)
                     const uint32_t canon = __builtin_amdgcn_perm(0x4E000000u, 0x47544341u, kk);
-                    // sum of |canon - byte| (one v_sad_u8): zero iff every byte is canonical, and
-                    // at most 40 dwords x 4 x 255 per tile, so it never wraps
-#if FQ_EXO3
-                    // (or the OR of byte ^ canon: nonzero iff some byte is not canonical)
+                    // the OR of byte ^ canon (one full-rate v_bitop3, where a v_sad_u8 sum issues at
+                    // half rate): nonzero iff some byte is not canonical
                     exo |= FULL ? (canon ^ sr) : ((canon ^ sr) & bms);
-#else
-                    exo = FULL ? __builtin_amdgcn_sad_u8(canon, sr, exo)
-                               : __builtin_amdgcn_sad_u8(canon & bms, sr & bms, exo);
-#endif
                     const uint32_t qm = FULL ? qw[j] : (qw[j] & bm);
                     qhi |= qm;
                     const uint32_t m80 = FULL ? k80 : (k80 & bm);
@@ -1555,12 +1344,7 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                     // which runs on the XTRA instantiations (with -m the merge variant's)
                     if (!LEAN && XTRA) tqf = __builtin_amdgcn_sad_u8(qm, 0u, tqf);
                     if (!LEAN) lr |= ~(qm + limr) & (0x80808080u & bm);         // q < cut_right threshold
-#if FQ_STG2
                     kkj[j] = kk;
-#else
-                    cc |= (kk & 0x03030303u) << (2 * j);
-                    nn4 |= ((kk >> 2) & 0x01010101u) << (2 * j);
-#endif
                 };
                 if (full) {
 #pragma unroll
@@ -1583,7 +1367,6 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
 #pragma unroll
                     for (int j = 0; j < 4; ++j) dword(j, std::false_type{});
                 }
-#if FQ_STG2
                 {
                     // the keys of dwords 0 and 2 (1 and 3) share each byte in nibbles: code field j at
                     // bits 2j of the byte and N flag j at bit 2j come out of two masked merges
@@ -1595,7 +1378,6 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xAC" : "=v"(cc) : "v"(m33), "v"(c13), "v"(p02));  // m33 ? p02 : c13
                     nn4 = ((p02 >> 2) & 0x11111111u) | (p13 & 0x44444444u);
                 }
-#endif
                 if (!LEAN) lowr = shift_in_sign(lowr, lr | (0u - lr));  // (sign set iff lr != 0)
                 // N flags are kept only for positions inside the read (later passes rely on it);
                 // read 2's chunk is reversed: its positions inside the read are the high ones
@@ -1607,12 +1389,8 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                 // read's rc position j sits at index j + (160 - L); garbage beyond L lands below.
                 // Complement: code ^ 2 for A C G T, N stays code 3.
                 fck ^= rcx & ~(fwk << 1);
-#if FQ_ABLATE_STAGE == 2  // profiling only: no LDS column writes (results invalid)
-                tqf ^= fck ^ fwk;
-#else
                 wp[kFC * 64] = fck;
                 wp[kFN * 64] = fwk;
-#endif
                 wp += wstep;
                 if constexpr (LY::kPfx)  // counts through chunk k (each <= 160): q20 | q30 << 8 | low << 16 | N << 24
                     if ((k + 1) % LY::kPfxStep == 0)
@@ -1703,48 +1481,10 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#if FQ_STAGE_PRIO || FQ_PRIO_TRIM
-        __builtin_amdgcn_s_setprio(FQ_PRIO_TRIM);  // (the phases after staging, up to polyG)
-#endif
-#if FQ_PREFETCH
-        // The wave's next tile is one contiguous run of R * stride bytes per plane (R = 32 pairs or
-        // 64 reads; planes span whole 32-read tiles, so the run is clamped to the rows that exist):
-        // one dword per 128-byte line, loaded into a never-read LDS sink, so the next staging finds
-        // its rows in L2 / the Infinity Cache while this tile computes.  The asm loads are outside
-        // hipcc's waitcnt bookkeeping; any later counted vmcnt wait covers them (older loads retire
-        // first), so nothing waits on them before the quality re-reads of the filter / stats.
-        {
-            const int tn = t + gridDim.x * kWaves;
-            if (tn < ntiles) {
-                constexpr int R = PAIRED ? 32 : 64;
-                const int rows = min(R, ((b.n + 31) & ~31) - tn * R);
-                // (PAIRED: the first FQ_PREFETCH chunks of the 32 rows, 512 B each)
-                const int run = PAIRED ? min(rows * b.stride, FQ_PREFETCH * 512) : rows * b.stride;
-                const uint32_t sink = (uint32_t)(LY::kLdsW - kPfW) * 4u;
-                const uint8_t* planes[4] = {b.seq1, b.qual1, b.seq2, b.qual2};
-#pragma unroll
-                for (int pi = 0; pi < (PAIRED ? 4 : 2); ++pi) {
-                    const uint8_t* base = planes[pi] + (size_t)tn * R * b.stride;
-                    for (int off = lane_x * 128; off < run; off += 64 * 128) {
-                        const uint8_t* g = base + off;
-                        unsigned keep;
-                        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                                     : "=&s"(keep) : "v"(g), "s"(sink));
-                    }
-                }
-            }
-        }
-#endif
-#if FQ_ABLATE_STAGE >= 3  // profiling only: staging, then straight to the result store
-        if (valid && res)
-            *reinterpret_cast<uint4*>(&res[PAIRED ? 2 * (size_t)idx + mate : (size_t)idx]) =
-                make_uint4(tqf, q20 + q30 + lowf + nbf, exo, FQ_ABLATE_STAGE == 4 ? L : 0);
-        continue;
-#endif
+        __builtin_amdgcn_s_setprio(kPrioTrim);  // (the phases after staging, up to polyG)
 
         FQ_STAMP(0)
         const CodeSeq seq{col, lane, rc};
-        const LdsQual qual{qrow};  // trimAndCut windows (full variant only)
 
         // ---------------- trimAndCut (src/peprocessor.cpp:292-293) ----------------
         int st = 0, n = 0;
@@ -1753,9 +1493,7 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
             nn = valid;
             n = L;
         } else {
-            if constexpr (LY::kQLds)
-                nn = valid && trim_and_cut_t(p, seq, qual, L, front, tail, st, n, lowr_ok ? lowr : ~0u);
-            else if (XTRA && umi) {
+            if (XTRA && umi) {
                 // UmiProcessor::process cuts min(umi_front, len - 1) bases (a read of length 0 keeps
                 // them), src/peprocessor.cpp:288-290 / src/seprocessor.cpp:309-311
                 const int uf = mate ? p.umi_front2 : p.umi_front1;
@@ -1781,9 +1519,7 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
 
         FQ_STAMP(1)
         // ---------------- polyG (src/peprocessor.cpp:295-299) ----------------
-#if FQ_PRIO_POLYG || FQ_PRIO_OV || FQ_PRIO_FILTER
-        __builtin_amdgcn_s_setprio(FQ_PRIO_POLYG);  // (issue priority by phase: FQ_PRIO_TRIM)
-#endif
+        __builtin_amdgcn_s_setprio(kPrioPolyG);  // (issue priority by phase: kPrioStage)
         if (both && p.polyg_enabled && !(abl & 8)) {
             int bases;
             n = polyg_bits(col, lane, rc, st, n, p.polyg_max_mismatch, g_inv, g_per, p.polyg_compare_req, bases);
@@ -1877,9 +1613,7 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
             return ov;
         };
         // ---------------- overlap + adapters (src/peprocessor.cpp:302-333) ----------------
-#if FQ_PRIO_POLYG || FQ_PRIO_OV || FQ_PRIO_FILTER
-        __builtin_amdgcn_s_setprio(FQ_PRIO_OV);
-#endif
+        __builtin_amdgcn_s_setprio(kPrioOv);
         Overlap ov1{0, 0, 0, 0};  // (merge) the first analysis and the windows it saw
         int n1a = -1, n2a = -1;
         bool ad_ov = false, corr = false;  // (corr: -c changed a base of the pair)
@@ -1978,9 +1712,7 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
 
         FQ_STAMP(4)
         // ---------------- passFilter (src/filter.cpp:3-52) ----------------
-#if FQ_PRIO_POLYG || FQ_PRIO_OV || FQ_PRIO_FILTER
-        __builtin_amdgcn_s_setprio(FQ_PRIO_FILTER);
-#endif
+        __builtin_amdgcn_s_setprio(kPrioFilter);
         int code = FQ_FAIL_LENGTH;
         uint32_t w20 = 0, w30 = 0;  // Q20/Q30 of the window, for the post stats
         int low = 0, tq = 0, nb = 0;
@@ -2030,10 +1762,10 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                 });
         } else if (nn && wn > 0) {
             // window sums = whole-read sums (from staging) minus the trimmed head [0, ws) and
-            // tail [ws+wn, L): the trimmed parts are usually a few bases.  (FULL: a window
-            // shorter than half the read, e.g. read 2's part of a merged read, is summed directly:
-            // "subtracted" from 0 and negated.)
-            const bool direct = (!LEAN || FQ_LEAN_DIRECT) && 2 * wn < L;
+            // tail [ws+wn, L): the trimmed parts are usually a few bases.  (A window shorter than
+            // half the read, e.g. read 2's part of a merged read, is summed directly: "subtracted"
+            // from 0 and negated.)
+            const bool direct = 2 * wn < L;
             low = direct ? 0 : (int)lowf;
             tq = direct ? 0 : (int)tqf;
             nb = direct ? 0 : (int)nbf;
@@ -2067,10 +1799,8 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                             if (need_tq) tq -= (int)__builtin_amdgcn_sad_u8(wq[j] & ((rf >> 7) * 0xFFu), 0u, 0u);
                         }
                     };
-#if FQ_FILTER_BATCH
-                    if ((!LEAN || FQ_LEAN_DIRECT) && a0 < a1) {
-                        // (FULL) the range's row chunks from L2, four requested together per round
-                        // trip (LEAN, whose ranges are the trimmed tails only, is faster as below)
+                    if (a0 < a1) {
+                        // the range's row chunks from L2, four requested together per round trip
                         for (int Fb = F0; Fb < F1; Fb += 4) {
                             uint4 qa[4];
 #pragma unroll
@@ -2079,36 +1809,7 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                             for (int i = 0; i < 4; ++i)
                                 if (Fb + i < F1) sub(qa[i], Fb + i);
                         }
-                    } else if (LEAN && part == 1 && a0 < a1) {
-                        uint4 qa[2];
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) qa[i] = qchunk(max(F1 - 1 - i, 0));
-#pragma unroll
-                        for (int i = 0; i < 2; ++i)
-                            if (F1 - 1 - i >= F0) sub(qa[i], F1 - 1 - i);
-                        for (int F = F1 - 3; F >= F0; --F) sub(qchunk(F), F);
                     }
-#else
-                    if (part == 1 && a0 < a1) {
-                        // the tail, from the 3' end: its last two chunks are requested together
-                        // (one L2 round trip for most reads), longer adapter tails loop
-                        uint4 qa[2];
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) qa[i] = qchunk(max(F1 - 1 - i, 0));
-#pragma unroll
-                        for (int i = 0; i < 2; ++i)
-                            if (F1 - 1 - i >= F0) sub(qa[i], F1 - 1 - i);
-                        for (int F = F1 - 3; F >= F0; --F) sub(qchunk(F), F);
-                    } else if (!LEAN) {
-                        // row chunks come from L2; the next one is requested before this one is used
-                        uint4 cur = qchunk(min(F0, nchunks - 1));
-                        for (int F = F0; F < F1; ++F) {
-                            const uint4 nxt = qchunk(min(F + 1, nchunks - 1));
-                            sub(cur, F);
-                            cur = nxt;
-                        }
-                    }
-#endif
                     // N bits of the same range (read 2's column is reverse-complemented)
                     const int s0 = rc ? kMaxLen - a1 : a0, s1 = rc ? kMaxLen - a0 : a1;
                     for (int c = s0 >> 4; c < ((s1 + 15) >> 4); ++c) {
@@ -2260,9 +1961,7 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                 sadd(&sc[9], ((unsigned long long)w20 << 32) | w30);
             }
         }
-#if FQ_STATS_PRIO
-        __builtin_amdgcn_s_setprio(FQ_STATS_PRIO);  // (the Stats pass: highest, FQ_PRIO_TRIM)
-#endif
+        __builtin_amdgcn_s_setprio(kPrioStats);  // (the Stats passes: highest, held to the end of the tile)
         if (valid && !(abl & 4) && removed_mode) {
             // Every kept window is a prefix [0, wlen): each base goes to exactly one cell, kept or
             // removed (pre = kept + removed at the flush), one LDS atomic per base.  Per chunk the
@@ -2272,12 +1971,7 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
             // post block at other cycles, below, and read 2's own bases only to its pre block)
             const int wlen = post_on && !(MERGE && merged && mate) ? wn : 0;
             const int dsel = r >> 2, rr4 = 4 * (r & 7);
-            [[maybe_unused]] const bool rswap = r >= 8;
-#if FQ_ST_VCC
-            // the lanes whose rotation takes the next dword / the other half (dsel & 2 == rswap)
-            const unsigned long long msel1 = __builtin_amdgcn_ballot_w64((dsel & 1) != 0);
-            const unsigned long long msel2 = __builtin_amdgcn_ballot_w64((dsel & 2) != 0);
-#endif
+            const bool rswap = r >= 8;
             // LDS byte address of rotated position t's cell in slot 0 of chunk 0 (this mate's rows):
             // bits 8-11 are clear, the slot nibble is or-ed in (rcell)
             static_assert((LY::kColsW * 4) % 4096 == 0, "removed-mode rows: 4 KiB aligned");
@@ -2290,7 +1984,7 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
             }
             const uint32_t slot_m = vk(0xF00u);
             // quality chunks rotate through kSA + 1 registers (requested kSA chunks ahead)
-            constexpr int kSA = FQ_STATS_AHEAD;
+            constexpr int kSA = 2;
             uint4 qb[kSA + 1];
 #pragma unroll
             for (int i = 0; i < kSA; ++i) qb[i] = qchunk(min(i, nchunks - 1));
@@ -2306,10 +2000,10 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                 }
                 return Fwd{cw, nw};
             };
-            // PF2: raw column words of chunks F and F + 1 (requested two chunks ahead: the wait for
+            // kPf2: raw column words of chunks F and F + 1 (requested two chunks ahead: the wait for
             // chunk F's words then does not cover the atomics issued since).  Two more live VGPRs:
             // the FULL non-merge variants would spill, so they read one chunk ahead.
-            constexpr bool kPf2 = FQ_ST_PF2 && (LEAN || (MERGE && !XTRA));
+            constexpr bool kPf2 = LEAN || (MERGE && !XTRA);
             uint32_t rw0c = 0, rw0n = 0, rw1c = 0, rw1n = 0;
             Fwd fn{0u, 0u};
             if constexpr (kPf2) {
@@ -2319,9 +2013,7 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
             } else {
                 fn = fwd_at(cwp);
             }
-#if FQ_ST_KM2
             const uint32_t m0f = vk(0x0F0F0F0Fu), m33 = vk(0x33333333u), m44 = vk(0x44444444u);
-#endif
             // nibble prefix masks from one 64-bit shift: ~(~0 << 4 * clamp(len, 0, 16)), the
             // 64th bit never needed (nibble 15's top bit is 0 in 0x4444... and 0xAAAA... masks)
             const int w4 = 4 * wlen, l4 = 4 * L;
@@ -2355,7 +2047,6 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                     }
                     const int vl = L - 16 * F;
                     // slot 4 * kept + code; an N (code 3) reads as a G here
-#if FQ_ST_KM2
                     // kept nibbles: ~(~0 << s), s = clamp(4 wlen - 64 F, 0, 63) (one v_med3); the
                     // codes spread to nibbles for both halves at once by 64-bit shifts, masked by
                     // one v_bitop3 per word, the kept bit or-ed in by another
@@ -2375,12 +2066,6 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                         lo = (~(uint32_t)km & m44) | z0;
                         hi = (~(uint32_t)(km >> 32) & m44) | z1;
                     }
-#else
-                    const unsigned long long km = ~(~0ull << min(max(w4 - 64 * F, 0), 63));
-                    uint32_t lo = spread2to4(f.c) + ((uint32_t)km & 0x44444444u);
-                    uint32_t hi = spread2to4(f.c >> 16) + ((uint32_t)(km >> 32) & 0x44444444u);
-#endif
-#if FQ_NFOLD
                     // N bases: their slot kRNSlot + 4 * kept is the G slot + 5, one nibble add (staging
                     // kept N flags only inside the read)
                     if (__any(f.n != 0)) {
@@ -2392,75 +2077,25 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                         lo += n05;
                         hi += n15;
                     }
-#endif
                     if (__any(vl < 16)) {  // positions beyond the read (kept is 0 there) -> dummy slot 10
                         const unsigned long long vm = ~0ull << min(max(l4 - 64 * F, 0), 63);
                         const uint32_t dlo = (uint32_t)vm, dhi = vl >= 16 ? 0u : (uint32_t)(vm >> 32);
                         lo = (lo & ~dlo) | (dlo & 0xAAAAAAAAu);
                         hi = (hi & ~dhi) | (dhi & 0xAAAAAAAAu);
                     }
-#if !FQ_NFOLD
-                    // N bases (profiling baseline): move each from its G cell (slot 4 * kept + 3) to
-                    // slot kRNSlot + 4 * kept
-                    uint32_t nv = f.n;
-                    if (__any(nv != 0)) {
-                        const uint32_t qs[4] = {q0, q1, q2, q3};
-                        while (nv) {
-                            const int t = (__ffs(nv) - 1) >> 1;
-                            nv &= nv - 1;
-                            const int kept = 16 * F + t < wlen ? 1 : 0;
-                            const unsigned long long v = kCount1 | (unsigned long long)__builtin_amdgcn_ubfe(qs[t >> 2], 8 * (t & 3), 8);
-                            const uint32_t a = (uint32_t)(LY::kColsW + mate * 32) * 4u +
-                                               (uint32_t)(F * kRSlots * 64 * 4) + 8u * (uint32_t)t;
-                            __hip_atomic_fetch_add(reinterpret_cast<LdsU64*>((size_t)(a + (uint32_t)(kRNSlot + 4 * kept) * 256u)), v,
-                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                            __hip_atomic_fetch_add(reinterpret_cast<LdsU64*>((size_t)(a + (uint32_t)(4 * kept + 3) * 256u)), 0ull - v,
-                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        }
-                    }
-#endif
                     // rotate by r positions: rotated position t is 16F + (t + r) % 16
-#if FQ_ST_VCC
-                    // (the ten selects against two per-lane masks: left to itself the compiler keeps
-                    // both masks in SGPR pairs and issues v_cndmask_b32_e64 at half rate; with the
-                    // mask in VCC the e32 form issues at full rate)
-                    uint32_t xa, xb, a0, a1, a2, a3;
-                    {
-                        uint32_t t0, t1, t2, t3;
-                        asm("s_mov_b64 vcc, %[m1]\n\t"
-                            "v_cndmask_b32_e32 %[t0], %[q0], %[q1], vcc\n\t"
-                            "v_cndmask_b32_e32 %[t1], %[q1], %[q2], vcc\n\t"
-                            "v_cndmask_b32_e32 %[t2], %[q2], %[q3], vcc\n\t"
-                            "v_cndmask_b32_e32 %[t3], %[q3], %[q0], vcc\n\t"
-                            "s_mov_b64 vcc, %[m2]\n\t"
-                            "v_cndmask_b32_e32 %[a0], %[t0], %[t2], vcc\n\t"
-                            "v_cndmask_b32_e32 %[a1], %[t1], %[t3], vcc\n\t"
-                            "v_cndmask_b32_e32 %[a2], %[t2], %[t0], vcc\n\t"
-                            "v_cndmask_b32_e32 %[a3], %[t3], %[t1], vcc\n\t"
-                            "v_cndmask_b32_e32 %[xa], %[lo], %[hi], vcc\n\t"
-                            "v_cndmask_b32_e32 %[xb], %[hi], %[lo], vcc"
-                            : [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [a0] "=&v"(a0),
-                              [a1] "=&v"(a1), [a2] "=&v"(a2), [a3] "=&v"(a3), [xa] "=&v"(xa), [xb] "=&v"(xb)
-                            : [m1] "s"(msel1), [m2] "s"(msel2), [q0] "v"(q0), [q1] "v"(q1), [q2] "v"(q2), [q3] "v"(q3),
-                              [lo] "v"(lo), [hi] "v"(hi)
-                            : "vcc");
-                    }
-                    const uint32_t klo = __builtin_amdgcn_alignbit(xb, xa, rr4), khi = __builtin_amdgcn_alignbit(xa, xb, rr4);
-#else
                     const uint32_t xa = rswap ? hi : lo, xb = rswap ? lo : hi;
                     const uint32_t klo = __builtin_amdgcn_alignbit(xb, xa, rr4), khi = __builtin_amdgcn_alignbit(xa, xb, rr4);
                     const uint32_t t0 = (dsel & 1) ? q1 : q0, t1 = (dsel & 1) ? q2 : q1;
                     const uint32_t t2 = (dsel & 1) ? q3 : q2, t3 = (dsel & 1) ? q0 : q3;
                     const uint32_t a0 = (dsel & 2) ? t2 : t0, a1 = (dsel & 2) ? t3 : t1;
                     const uint32_t a2 = (dsel & 2) ? t0 : t2, a3 = (dsel & 2) ? t1 : t3;
-#endif
                     // quality bytes (< 128 here): the low word of a cell increment
                     const uint32_t qr[4] = {__builtin_amdgcn_alignbyte(a1, a0, r & 3), __builtin_amdgcn_alignbyte(a2, a1, r & 3),
                                             __builtin_amdgcn_alignbyte(a3, a2, r & 3), __builtin_amdgcn_alignbyte(a0, a3, r & 3)};
                     // slot nibble t % 8 at bits 8-11: a right shift of the word (nibbles 2-7) or of the
                     // word shifted left by 8 (nibbles 0-1; one 64-bit shift gives both words' copies,
                     // the high one with klo's top byte in its low bits, masked off)
-#if FQ_ST_SH64
                     // nibble u of both words to bits 8-11 by one 64-bit shift of {khi, klo} (its low
                     // word: klo's nibble u, its high word: khi's): steps t and t + 8 share it
                     const unsigned long long K = (unsigned long long)khi << 32 | klo;
@@ -2473,19 +2108,10 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                         else if (u < 2) asm("v_lshlrev_b64 %0, %2, %1" : "=v"(Ks[u]) : "v"(K), "i"(8 - 4 * u));
                         else asm("v_lshrrev_b64 %0, %2, %1" : "=v"(Ks[u]) : "v"(K), "i"(4 * (u - 2)));
                     }
-#else
-                    const unsigned long long k8 = ((unsigned long long)khi << 32 | klo) << 8;
-                    const uint32_t klo8 = (uint32_t)k8, khi8 = (uint32_t)(k8 >> 32);
-#endif
 #pragma unroll
                     for (int t = 0; t < 16; ++t) {
                         const int u = t & 7;
-#if FQ_ST_SH64
                         const uint32_t ksh = t < 8 ? (uint32_t)Ks[u] : (uint32_t)(Ks[u] >> 32);
-#else
-                        const uint32_t kw = u < 2 ? (t < 8 ? klo8 : khi8) : (t < 8 ? klo : khi);
-                        const uint32_t ksh = u < 2 ? kw >> (4 * u) : kw >> (4 * (u - 2));
-#endif
                         // (byte 0 and 3 by one full-rate op, 1 and 2 by a bit-field extract)
                         const uint32_t qw = qr[t >> 2];
                         const uint32_t qv = (t & 3) == 0 ? qw & 0xFFu : (t & 3) == 3 ? qw >> 24 : __builtin_amdgcn_ubfe(qw, 8 * (t & 3), 8);
@@ -2498,9 +2124,6 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                 }
             }
         }
-#if FQ_STATS_PRIO && !FQ_STATS_PRIO_ALL
-        __builtin_amdgcn_s_setprio(0);
-#endif
         // read 2's merged-part start, known to both lanes of the pair (all lanes swap)
         const int ws2 = MERGE ? (mate ? ws : xor32(ws)) : 0;
         if (MERGE && removed_mode && valid && !(abl & 4) && merged && post_on) {
@@ -2516,199 +2139,103 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
             const int c2 = lane_x | 32;  // read 2's column
             const int pos_hi = ws2 + m2 - 1;
             const int ci0 = kMaxLen - 1 - pos_hi;
-            // FQ_MERGE_ROTATE=1: each lane walks its groups rotated by rl = (lane - m1) % 16
-            // positions: at step t it takes part position 16 J + (t + rl) % 16, merged cycle c with
-            // c % 16 = (t + lane) % 16, so the 16 lanes of an LDS group hit 16 bank pairs whatever
-            // their m1.  Unrotated (the default), the cycles of a step depend on m1 and collide: 39 %
-            // of the C4 kernel's LDS cycles are bank conflicts, 4.6 % rotated -- but the rotation's
-            // VALU (+104 per tile) costs more than the conflicts (C4 +1-2 % per launch,
-            // profiles/r04_ab_merge_rotate.txt): the LDS waits overlap other waves' VALU.
+            // The lane takes part position 16 J + t at step t, so the cycles of a step depend on m1 and
+            // collide in LDS banks (39 % of the C4 kernel's LDS cycles are bank conflicts).  Walking the
+            // groups rotated by (lane - m1) % 16 brings that to 4.6 %, but the rotation's VALU (+104 per
+            // tile) costs more than the conflicts (C4 +1-2 % per launch, profiles/r04_ab_merge_rotate.txt):
+            // the LDS waits overlap other waves' VALU.
             // rb[t]: byte address of step t's slot-0 cell (mcell) for the lane's next J.
             static_assert((LY::kColsW + LY::kMrgOff) % 256 == 0, "merged-part rows: 1 KiB aligned");
-            constexpr bool kRot = FQ_MERGE_ROTATE != 0;
-            const int rl = kRot ? (lane_x - m1) & 15 : 0;
             uint32_t rb[16];
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
-                const int c = m1 + ((t + rl) & 15) + 16 * mate;
+                const int c = m1 + t + 16 * mate;
                 rb[t] = xb + (uint32_t)((c >> 4) << 10 | (c & 15) << 3);
                 asm volatile("" : "+v"(rb[t]));
             }
             const uint32_t mslot_m = vk(0x380u);
-            const bool mswap = rl >= 8;
-            const int rr4m = 4 * (rl & 7);
-            // qualities: qa is in reversed position order v = 15 - u (byte v % 4 of qa[v / 4]);
-            // rotated by rv = -rl bytes, step t's byte is at reversed index 15 - t
-            const int rv = (16 - rl) & 15, vsel = rv >> 2;
             // quality dwords of forward positions [hi - 15, hi], hi = pos_hi - 16J: words
             // wl0 - 4J .. wl0 - 4J + 4; the lane's next group (J + 2) is requested one group ahead
             const int wl0 = (pos_hi - 15) >> 2, sh = (pos_hi - 15) & 3;  // (negative only for dummies)
-            const uint8_t* Q2 = b.qual2 + roff;
-            const uint32_t* qrow2 = qrows + c2 * kQS;
-            auto qword = [&](int wi) -> uint32_t {
-                if constexpr (LY::kQLds) return qrow2[min(max(wi, 0), kQS - 1)];
-                else return RowQual{Q2, b.stride >> 2}.word(max(wi, 0));
-            };
             uint32_t qw5[5];
-#if FQ_MRG2
-            if constexpr (!kRot && !LY::kQLds) {
-                // The lane's groups J = mate + 2k unrolled (k < kMrgIter): the cell rows of group k are
-                // 2048 k bytes on (an immediate of the atomics), and its quality dwords 1024 k bytes
-                // back in the row.  The dwords come through a buffer over the wave's tile of read 2's
-                // quality plane: an offset outside the tile (a dummy position before the row) reads 0
-                // instead of faulting, so no clamping; the 5 offsets are computed once.
-                constexpr int kMrgIter = (kMaxLen + 31) / 32;
-                const size_t tile_off = (size_t)__builtin_amdgcn_readfirstlane(t) * FQ_TILE_READS * (size_t)b.stride;
-                const __amdgpu_buffer_rsrc_t qr2 = __builtin_amdgcn_make_buffer_rsrc(
-                    (void*)(b.qual2 + tile_off), (short)0, FQ_TILE_READS * b.stride, 0x00020000);
-                int vo[5];
+            // The lane's groups J = mate + 2k unrolled (k < kMrgIter): the cell rows of group k are
+            // 2048 k bytes on (an immediate of the atomics), and its quality dwords 1024 k bytes
+            // back in the row.  The dwords come through a buffer over the wave's tile of read 2's
+            // quality plane: an offset outside the tile (a dummy position before the row) reads 0
+            // instead of faulting, so no clamping; the 5 offsets are computed once.
+            constexpr int kMrgIter = (kMaxLen + 31) / 32;
+            const size_t tile_off = (size_t)__builtin_amdgcn_readfirstlane(t) * FQ_TILE_READS * (size_t)b.stride;
+            const __amdgpu_buffer_rsrc_t qr2 = __builtin_amdgcn_make_buffer_rsrc(
+                (void*)(b.qual2 + tile_off), (short)0, FQ_TILE_READS * b.stride, 0x00020000);
+            int vo[5];
 #pragma unroll
-                for (int i = 0; i < 5; ++i) {
-                    const int w = wl0 - 4 * mate + i;
-                    vo[i] = (w >> 2) * (FQ_TILE_READS * FQ_CHUNK) + ((w & 3) << 2) + pl * FQ_CHUNK;
-                }
-#pragma unroll
-                for (int i = 0; i < 5; ++i) qw5[i] = __builtin_amdgcn_raw_buffer_load_b32(qr2, vo[i], 0, 0);
-                // slot nibble to bits 7-9: nibble u of both words by one 64-bit shift (as FQ_ST_SH64)
-#pragma unroll
-                for (int k = 0; k < kMrgIter; ++k) {
-                    const int J = mate + 2 * k;
-                    if (!__any(16 * J < m2)) break;  // (wave-uniform)
-                    if (16 * J < m2) {
-                        const uint32_t cw = field_window_masked(col, kFC, c2, ci0 + 16 * J);
-                        const uint32_t nw = field_window_masked(col, kFN, c2, ci0 + 16 * J);
-                        uint32_t qn[5] = {0u, 0u, 0u, 0u, 0u};
-                        if (k + 1 < kMrgIter)
-#pragma unroll
-                            for (int i = 0; i < 5; ++i) qn[i] = __builtin_amdgcn_raw_buffer_load_b32(qr2, vo[i] - 1024 * (k + 1), 0, 0);
-                        uint32_t qa[4];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) qa[i] = __builtin_amdgcn_alignbyte(qw5[i + 1], qw5[i], sh);
-                        auto qbyte = [&](int tt) -> uint32_t {  // step tt: part position tt, byte 3 - tt % 4 of qa[3 - tt / 4]
-                            const uint32_t qw = qa[(15 - tt) >> 2];
-                            const int bs = (15 - tt) & 3;
-                            return bs == 0 ? qw & 0xFFu : bs == 3 ? qw >> 24 : __builtin_amdgcn_ubfe(qw, 8 * bs, 8);
-                        };
-                        const int rem = m2 - 16 * J;
-                        const unsigned long long dm = ~0ull << min(4 * max(rem, 0), 63);
-                        uint32_t nlo = spread2to4(cw), nhi = spread2to4(cw >> 16);
-                        const uint32_t dlo = (uint32_t)dm, dhi = rem >= 16 ? 0u : (uint32_t)(dm >> 32);
-                        nlo = (nlo & ~dlo) | (dlo & 0x55555555u);  // 5 = kDummySlot
-                        nhi = (nhi & ~dhi) | (dhi & 0x55555555u);
-                        // nibble u of {nhi, nlo} to bits 7-9: K << 7 (u 0), K << 3 (u 1), K >> (4u - 7)
-                        const unsigned long long K = (unsigned long long)nhi << 32 | nlo;
-                        unsigned long long Ks[8];
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) {
-                            if (u < 2) asm("v_lshlrev_b64 %0, %2, %1" : "=v"(Ks[u]) : "v"(K), "i"(7 - 4 * u));
-                            else asm("v_lshrrev_b64 %0, %2, %1" : "=v"(Ks[u]) : "v"(K), "i"(4 * u - 7));
-                        }
-#pragma unroll
-                        for (int tt = 0; tt < 16; ++tt) {
-                            const uint32_t ksh = tt < 8 ? (uint32_t)Ks[tt & 7] : (uint32_t)(Ks[tt & 7] >> 32);
-                            uint32_t a;
-                            asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xEA" : "=v"(a) : "v"(ksh), "v"(mslot_m), "v"(rb[tt]));
-                            a += 2048u * (uint32_t)k;  // (folds into the ds offset)
-                            __hip_atomic_fetch_add(reinterpret_cast<LdsU64*>((size_t)a), kCount1 | (unsigned long long)qbyte(tt),
-                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        }
-                        uint32_t nv = nw & posmask(rem);
-                        while (nv) {  // N (code 3): from the G slot (3) to the N slot (4)
-                            const int tt = (__ffs(nv) - 1) >> 1;
-                            nv &= nv - 1;
-                            const unsigned long long v =
-                                kCount1 | (unsigned long long)__builtin_amdgcn_ubfe(qa[3 - (tt >> 2)], 8 * (3 - (tt & 3)), 8);
-                            const int c = m1 + 16 * J + tt;
-                            const uint32_t a = xb + (uint32_t)((c >> 4) << 10 | (c & 15) << 3);
-                            __hip_atomic_fetch_add(reinterpret_cast<LdsU64*>((size_t)(a + 4u * 128u)), v, __ATOMIC_RELAXED,
-                                                   __HIP_MEMORY_SCOPE_WORKGROUP);
-                            __hip_atomic_fetch_add(reinterpret_cast<LdsU64*>((size_t)(a + 3u * 128u)), 0ull - v,
-                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        }
-#pragma unroll
-                        for (int i = 0; i < 5; ++i) qw5[i] = qn[i];
-                    }
-                }
-            } else
-#endif
-            {
-#pragma unroll
-            for (int i = 0; i < 5; ++i) qw5[i] = qword(wl0 - 4 * mate + i);
-            for (int J = mate; 16 * J < m2; J += 2) {
-                // (ci0 >= 0; positions past the part are the dummy slot / masked by rem)
-                const uint32_t cw = field_window_masked(col, kFC, c2, ci0 + 16 * J);
-                const uint32_t nw = field_window_masked(col, kFN, c2, ci0 + 16 * J);
-                uint32_t qn[5];
-#pragma unroll
-                for (int i = 0; i < 5; ++i) qn[i] = qword(wl0 - 4 * (J + 2) + i);
-                // qualities ascending in qa[0..3]: part position u is byte 3 - u % 4 of qa[3 - u / 4]
-                uint32_t qa[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) qa[i] = __builtin_amdgcn_alignbyte(qw5[i + 1], qw5[i], sh);
-                // rotated: reversed index x = 4k + b is byte b of qv4[k], position u = (15 - x + rl) % 16
-                uint32_t qv4[4] = {qa[0], qa[1], qa[2], qa[3]};
-                if constexpr (kRot) {
-                const uint32_t t0 = (vsel & 1) ? qa[1] : qa[0], t1 = (vsel & 1) ? qa[2] : qa[1];
-                const uint32_t t2 = (vsel & 1) ? qa[3] : qa[2], t3 = (vsel & 1) ? qa[0] : qa[3];
-                const uint32_t a0 = (vsel & 2) ? t2 : t0, a1 = (vsel & 2) ? t3 : t1;
-                const uint32_t a2 = (vsel & 2) ? t0 : t2, a3 = (vsel & 2) ? t1 : t3;
-                qv4[0] = __builtin_amdgcn_alignbyte(a1, a0, rv & 3), qv4[1] = __builtin_amdgcn_alignbyte(a2, a1, rv & 3);
-                qv4[2] = __builtin_amdgcn_alignbyte(a3, a2, rv & 3), qv4[3] = __builtin_amdgcn_alignbyte(a0, a3, rv & 3);
-                }
-                auto qbyte = [&](int t) -> uint32_t {  // step t (bytes 0 and 3 by one full-rate op)
-                    const uint32_t qw = qv4[(15 - t) >> 2];
-                    const int bs = (15 - t) & 3;
-                    return bs == 0 ? qw & 0xFFu : bs == 3 ? qw >> 24 : __builtin_amdgcn_ubfe(qw, 8 * bs, 8);
-                };
-                // slot nibbles: code, or the dummy slot beyond the part
-                const int rem = m2 - 16 * J;
-                const unsigned long long dm = ~0ull << min(4 * max(rem, 0), 63);
-                uint32_t nlo = spread2to4(cw), nhi = spread2to4(cw >> 16);
-                const uint32_t dlo = (uint32_t)dm, dhi = rem >= 16 ? 0u : (uint32_t)(dm >> 32);
-                nlo = (nlo & ~dlo) | (dlo & 0x55555555u);  // 5 = kDummySlot
-                nhi = (nhi & ~dhi) | (dhi & 0x55555555u);
-                // rotated by rl nibbles: nibble t of {khi:klo} is part position (t + rl) % 16
-                uint32_t klo = nlo, khi = nhi;
-                if constexpr (kRot) {
-                    const uint32_t xa = mswap ? nhi : nlo, xb2 = mswap ? nlo : nhi;
-                    klo = __builtin_amdgcn_alignbit(xb2, xa, rr4m), khi = __builtin_amdgcn_alignbit(xa, xb2, rr4m);
-                }
-                // slot nibble t % 8 to bits 7-9 by one right shift (of the words shifted left by 8
-                // for nibbles 0-1, as in the removed-mode pass above), or-ed into the cell address
-                const unsigned long long k8 = ((unsigned long long)khi << 32 | klo) << 8;
-                const uint32_t nlo8 = (uint32_t)k8, nhi8 = (uint32_t)(k8 >> 32);
-#pragma unroll
-                for (int t = 0; t < 16; ++t) {
-                    const int u = t & 7;
-                    const uint32_t ksh = u < 2 ? (t < 8 ? nlo8 : nhi8) >> (4 * u + 1) : (t < 8 ? klo : khi) >> (4 * u - 7);
-                    uint32_t a;
-                    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xEA" : "=v"(a) : "v"(ksh), "v"(mslot_m), "v"(rb[t]));
-                    __hip_atomic_fetch_add(reinterpret_cast<LdsU64*>((size_t)a), kCount1 | (unsigned long long)qbyte(t),
-                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-                uint32_t nv = nw & posmask(rem);
-                while (nv) {  // N (code 3): from the G slot (3) to the N slot (4)
-                    const int t = (__ffs(nv) - 1) >> 1;
-                    nv &= nv - 1;
-                    const unsigned long long v =
-                        kCount1 | (unsigned long long)__builtin_amdgcn_ubfe(qa[3 - (t >> 2)], 8 * (3 - (t & 3)), 8);
-                    const int c = m1 + 16 * J + t;  // (rb[t] recomputed: t is not a constant)
-                    const uint32_t a = xb + (uint32_t)((c >> 4) << 10 | (c & 15) << 3);
-                    __hip_atomic_fetch_add(reinterpret_cast<LdsU64*>((size_t)(a + 4u * 128u)), v, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_WORKGROUP);
-                    __hip_atomic_fetch_add(reinterpret_cast<LdsU64*>((size_t)(a + 3u * 128u)), 0ull - v,
-                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-#pragma unroll
-                for (int i = 0; i < 5; ++i) qw5[i] = qn[i];
-#pragma unroll
-                for (int t = 0; t < 16; ++t) rb[t] += 2048u;  // (J + 2: two cycle rows on)
+            for (int i = 0; i < 5; ++i) {
+                const int w = wl0 - 4 * mate + i;
+                vo[i] = (w >> 2) * (FQ_TILE_READS * FQ_CHUNK) + ((w & 3) << 2) + pl * FQ_CHUNK;
             }
+#pragma unroll
+            for (int i = 0; i < 5; ++i) qw5[i] = __builtin_amdgcn_raw_buffer_load_b32(qr2, vo[i], 0, 0);
+            // slot nibble to bits 7-9: nibble u of both words by one 64-bit shift (as in the removed-mode pass above)
+#pragma unroll
+            for (int k = 0; k < kMrgIter; ++k) {
+                const int J = mate + 2 * k;
+                if (!__any(16 * J < m2)) break;  // (wave-uniform)
+                if (16 * J < m2) {
+                    const uint32_t cw = field_window_masked(col, kFC, c2, ci0 + 16 * J);
+                    const uint32_t nw = field_window_masked(col, kFN, c2, ci0 + 16 * J);
+                    uint32_t qn[5] = {0u, 0u, 0u, 0u, 0u};
+                    if (k + 1 < kMrgIter)
+#pragma unroll
+                        for (int i = 0; i < 5; ++i) qn[i] = __builtin_amdgcn_raw_buffer_load_b32(qr2, vo[i] - 1024 * (k + 1), 0, 0);
+                    uint32_t qa[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) qa[i] = __builtin_amdgcn_alignbyte(qw5[i + 1], qw5[i], sh);
+                    auto qbyte = [&](int tt) -> uint32_t {  // step tt: part position tt, byte 3 - tt % 4 of qa[3 - tt / 4]
+                        const uint32_t qw = qa[(15 - tt) >> 2];
+                        const int bs = (15 - tt) & 3;
+                        return bs == 0 ? qw & 0xFFu : bs == 3 ? qw >> 24 : __builtin_amdgcn_ubfe(qw, 8 * bs, 8);
+                    };
+                    const int rem = m2 - 16 * J;
+                    const unsigned long long dm = ~0ull << min(4 * max(rem, 0), 63);
+                    uint32_t nlo = spread2to4(cw), nhi = spread2to4(cw >> 16);
+                    const uint32_t dlo = (uint32_t)dm, dhi = rem >= 16 ? 0u : (uint32_t)(dm >> 32);
+                    nlo = (nlo & ~dlo) | (dlo & 0x55555555u);  // 5 = kDummySlot
+                    nhi = (nhi & ~dhi) | (dhi & 0x55555555u);
+                    // nibble u of {nhi, nlo} to bits 7-9: K << 7 (u 0), K << 3 (u 1), K >> (4u - 7)
+                    const unsigned long long K = (unsigned long long)nhi << 32 | nlo;
+                    unsigned long long Ks[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        if (u < 2) asm("v_lshlrev_b64 %0, %2, %1" : "=v"(Ks[u]) : "v"(K), "i"(7 - 4 * u));
+                        else asm("v_lshrrev_b64 %0, %2, %1" : "=v"(Ks[u]) : "v"(K), "i"(4 * u - 7));
+                    }
+#pragma unroll
+                    for (int tt = 0; tt < 16; ++tt) {
+                        const uint32_t ksh = tt < 8 ? (uint32_t)Ks[tt & 7] : (uint32_t)(Ks[tt & 7] >> 32);
+                        uint32_t a;
+                        asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xEA" : "=v"(a) : "v"(ksh), "v"(mslot_m), "v"(rb[tt]));
+                        a += 2048u * (uint32_t)k;  // (folds into the ds offset)
+                        __hip_atomic_fetch_add(reinterpret_cast<LdsU64*>((size_t)a), kCount1 | (unsigned long long)qbyte(tt),
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                    uint32_t nv = nw & posmask(rem);
+                    while (nv) {  // N (code 3): from the G slot (3) to the N slot (4)
+                        const int tt = (__ffs(nv) - 1) >> 1;
+                        nv &= nv - 1;
+                        const unsigned long long v =
+                            kCount1 | (unsigned long long)__builtin_amdgcn_ubfe(qa[3 - (tt >> 2)], 8 * (3 - (tt & 3)), 8);
+                        const int c = m1 + 16 * J + tt;
+                        const uint32_t a = xb + (uint32_t)((c >> 4) << 10 | (c & 15) << 3);
+                        __hip_atomic_fetch_add(reinterpret_cast<LdsU64*>((size_t)(a + 4u * 128u)), v, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_WORKGROUP);
+                        __hip_atomic_fetch_add(reinterpret_cast<LdsU64*>((size_t)(a + 3u * 128u)), 0ull - v,
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 5; ++i) qw5[i] = qn[i];
+                }
             }
         }
-#if FQ_STATS_PRIO && FQ_STATS_PRIO_ALL == 1
-        __builtin_amdgcn_s_setprio(0);
-#endif
         if (valid && !(abl & 4) && !removed_mode) {
             const int wlen = post_on ? wn : 0;  // post window [ws, ws + wlen)
             // merged pairs: both parts go to read 1's post block, read 2's part reversed and
@@ -2900,7 +2427,7 @@ extern "C" __attribute__((visibility("default"))) int fq_debug_phase_cycles(unsi
 }
 #define FQ_PREPARE fq_pe_fast_prepare
 #define FQ_LAUNCH fq_launch_pe_fast
-#else  // the long-read build (pe_fast_long.hip): no merge variant
+#else  // the long-read build (pe_fast_long.hip)
 #define FQ_PREPARE fq_pe_fast_long_prepare
 #define FQ_LAUNCH fq_launch_pe_fast_long
 #endif
@@ -2925,13 +2452,13 @@ hipError_t FQ_PREPARE() {
     // the -c / UMI instantiations of the full variants
     if ((e = set_lds<false, true, false, true>()) != hipSuccess) return e;
     if ((e = set_lds<false, false, false, true>()) != hipSuccess) return e;
-#if FQ_MAXLEN == 160
+    // the merge variants
     if ((e = set_lds<false, true, true, false>()) != hipSuccess) return e;
     if ((e = set_lds<false, true, true, true>()) != hipSuccess) return e;
+#if FQ_MAXLEN == 160
     return fq_pe_fast_long_prepare();
 #else
-    if ((e = set_lds<false, true, true, false>()) != hipSuccess) return e;
-    return set_lds<false, true, true, true>();
+    return hipSuccess;
 #endif
 }
 
