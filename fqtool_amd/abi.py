@@ -109,6 +109,25 @@ class FqTextOut(ctypes.Structure):
     _fields_ = [("text", ctypes.c_void_p * 2), ("bytes", ctypes.c_uint64 * 2)]
 
 
+# routed egress (fq_engine_set_egress): the six output streams
+FQ_EG_OUT1, FQ_EG_OUT2, FQ_EG_MERGED, FQ_EG_UNPAIRED1, FQ_EG_UNPAIRED2, FQ_EG_FAILED = range(6)
+FQ_EG_STREAMS = 6
+
+
+class FqEgress(ctypes.Structure):  # fq_egress
+    _fields_ = [("open", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class FqEgressOut(ctypes.Structure):  # fq_egress_out
+    _fields_ = [("text", ctypes.c_void_p * FQ_EG_STREAMS), ("cap", ctypes.c_uint64 * FQ_EG_STREAMS),
+                ("bytes", ctypes.c_uint64 * FQ_EG_STREAMS)]
+
+
+class FqRawEgressOut(ctypes.Structure):  # fq_raw_egress_out
+    _fields_ = [("eg", FqEgressOut), ("adapters", ctypes.c_void_p * 2), ("adapter_cap", ctypes.c_uint64 * 2),
+                ("adapter_bytes", ctypes.c_uint64 * 2)]
+
+
 FQ_E_NO_DEVICE = -2
 FQ_INFLATE_MAX = 65536
 FQ_INFL_OK, FQ_INFL_DATA, FQ_INFL_LONG, FQ_INFL_SHORT, FQ_INFL_CRC = 0, 1, 2, 3, 4
@@ -301,6 +320,11 @@ def load_engine(path=ENGINE_LIB):
     lib.fq_deflate_destroy.argtypes = [vp]
     lib.fq_deflate_bgzf.argtypes = [vp, vp, ctypes.c_size_t, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     lib.fq_engine_set_gz_out.argtypes = [vp, i32]
+    lib.fq_egress_bound.argtypes = [i32, u64, u64, u64]
+    lib.fq_egress_bound.restype = ctypes.c_size_t
+    lib.fq_engine_set_egress.argtypes = [vp, ctypes.POINTER(FqEgress)]
+    lib.fq_engine_submit_text_routed.argtypes = [vp, ctypes.POINTER(FqTextBatch), vp, ctypes.POINTER(FqEgressOut), u64]
+    lib.fq_engine_raw_launch_routed.argtypes = [vp, ctypes.POINTER(FqRawResult), ctypes.POINTER(FqRawEgressOut), u64]
     cs = ctypes.c_size_t
     lib.fq_inflate_create.argtypes = [ctypes.c_int, cs, cs, cs, ctypes.POINTER(vp)]
     lib.fq_inflate_destroy.argtypes = [vp]
@@ -320,7 +344,7 @@ ENGINE_SYMBOLS = [
     "fq_dup_stat", "fq_kmer_open", "fq_kmer_close", "fq_kmer_count", "fq_kmer_find",
     "fq_engine_raw_begin", "fq_engine_raw_enqueue", "fq_engine_raw_launch", "fq_engine_raw_wait", "fq_engine_raw_end", "fq_host_register", "fq_host_unregister",
     "fq_deflate_bound", "fq_deflate_code_lengths", "fq_deflate_create", "fq_deflate_destroy", "fq_deflate_bgzf",
-    "fq_engine_set_gz_out",
+    "fq_engine_set_gz_out", "fq_egress_bound", "fq_engine_set_egress", "fq_engine_submit_text_routed", "fq_engine_raw_launch_routed",
     "fq_inflate_create", "fq_inflate_destroy", "fq_inflate_members", "fq_inflate_bgzf", "fq_inflate_last_kernel_ms",
     "fq_kstat_create", "fq_kstat_destroy", "fq_kstat_reset", "fq_kstat_k", "fq_kstat_words", "fq_engine_set_kstat",
     "fq_kstat_read", "fq_kstat_last_kernel_ms",

@@ -53,6 +53,16 @@ struct Slot {
     unsigned long long* d_total = nullptr;  // [2]
     unsigned long long* h_total = nullptr;  // pinned [2]
     fq_text_out* text_out = nullptr;        // the pending text pack's output descriptor
+    // routed egress (fq_engine_submit_text_routed): per open stream sizes, cursors and output text
+    uint32_t* d_egsize[FQ_EG_STREAMS] = {};
+    uint32_t* d_egoff[FQ_EG_STREAMS] = {};
+    char* d_eg[FQ_EG_STREAMS] = {};
+    size_t eg_cap[FQ_EG_STREAMS] = {};
+    size_t eg_recs[FQ_EG_STREAMS] = {};
+    unsigned long long* d_egtotal = nullptr;  // [FQ_EG_STREAMS]
+    unsigned long long* h_egtotal = nullptr;  // pinned
+    fq_egress_out* eg_out = nullptr;          // the pending routed pack's output descriptor
+    fq_raw_egress_out* reg_out = nullptr;     // ... of a routed raw pack: its adapter entries too (from d_ad)
     // raw windows (fq_engine_raw_*): line index, block counts / bases, indexing state, adapter entries
     uint32_t* d_lines[2] = {nullptr, nullptr};
     uint32_t* d_bcnt[2] = {nullptr, nullptr};
@@ -118,6 +128,9 @@ struct fq_engine {
     // engine (its launches all run on the compute stream, one after another)
     int gz_level = 0;
     fq_deflate_scratch gz;
+    // routed egress (fq_engine_set_egress): the streams that have a writer
+    bool eg_on = false;
+    uint32_t eg_open = 0;
     uint64_t calls = 0;       // order of process / process_device packs for the table
     std::string last_error;
 };
@@ -211,6 +224,13 @@ static void free_slot(Slot& s) {
     if (s.d_scan) (void)hipFree(s.d_scan);
     if (s.d_total) (void)hipFree(s.d_total);
     if (s.h_total) (void)hipHostFree(s.h_total);
+    for (int k = 0; k < FQ_EG_STREAMS; ++k) {
+        if (s.d_egsize[k]) (void)hipFree(s.d_egsize[k]);
+        if (s.d_egoff[k]) (void)hipFree(s.d_egoff[k]);
+        if (s.d_eg[k]) (void)hipFree(s.d_eg[k]);
+    }
+    if (s.d_egtotal) (void)hipFree(s.d_egtotal);
+    if (s.h_egtotal) (void)hipHostFree(s.h_egtotal);
     for (int m = 0; m < 2; ++m) {
         if (s.d_lines[m]) (void)hipFree(s.d_lines[m]);
         if (s.d_bcnt[m]) (void)hipFree(s.d_bcnt[m]);
@@ -431,7 +451,18 @@ static int issue_copies(fq_engine* e, int upto) {
             LinkChain& lc = link_chain(e->device);
             std::lock_guard<std::mutex> g(lc.m);
             if (lc.out && lc.out_owner != e) HIP_TRY(e, hipStreamWaitEvent(e->s_out, lc.out, 0));
-            for (int m = 0; m < 2 && !prof_no_egress(); ++m) {
+            for (int k = 0; k < FQ_EG_STREAMS && s.eg_out; ++k) {  // a routed pack: each open stream's text
+                // (a total above the caller's capacity copies nothing and fails the pack at retire)
+                const size_t bytes = (size_t)s.h_egtotal[k];
+                if (bytes && s.eg_out->text[k] && bytes <= s.eg_out->cap[k] && bytes <= s.eg_cap[k])
+                    HIP_TRY(e, hipMemcpyAsync(s.eg_out->text[k], s.d_eg[k], bytes, hipMemcpyDeviceToHost, e->s_out));
+            }
+            for (int m = 0; m < 2 && s.reg_out; ++m) {  // a routed raw pack: its trimmed-adapter entries
+                const unsigned long long ad = s.h_total[2 + m];
+                if (ad && ad != ~0ull && s.reg_out->adapters[m] && ad <= s.reg_out->adapter_cap[m])
+                    HIP_TRY(e, hipMemcpyAsync(s.reg_out->adapters[m], s.d_ad[m], (size_t)ad, hipMemcpyDeviceToHost, e->s_out));
+            }
+            for (int m = 0; m < 2 && !prof_no_egress() && !s.eg_out; ++m) {
                 if (!s.copy_dst[m]) continue;
                 const unsigned long long ad = s.h_total[2 + m];  // (~0: the entries overflowed, reported at retire)
                 const size_t bytes = std::min<size_t>(s.copy_cap[m], (size_t)s.h_total[m] + (ad == ~0ull ? 0 : (size_t)ad));
@@ -464,6 +495,26 @@ static int retire_slot(fq_engine* e, int k) {
         s.text_out->bytes[0] = s.h_total[0];
         s.text_out->bytes[1] = s.h_total[1];
         s.text_out = nullptr;
+    }
+    if (s.eg_out) {  // a routed pack: its streams' sizes
+        fq_egress_out* o = s.eg_out;
+        fq_raw_egress_out* ro = s.reg_out;
+        s.eg_out = nullptr;
+        s.reg_out = nullptr;
+        for (int k = 0; k < FQ_EG_STREAMS; ++k) {
+            o->bytes[k] = s.h_egtotal[k];
+            if (o->bytes[k] > o->cap[k] || o->bytes[k] > s.eg_cap[k]) {
+                o->bytes[k] = 0;
+                return fail(e, FQ_E_INVALID, "routed pack: a stream exceeds its buffer");
+            }
+        }
+        for (int m = 0; m < 2 && ro; ++m) {
+            ro->adapter_bytes[m] = s.h_total[2 + m];
+            if (ro->adapter_bytes[m] == ~0ull || ro->adapter_bytes[m] > ro->adapter_cap[m]) {
+                ro->adapter_bytes[m] = 0;
+                return fail(e, FQ_E_INVALID, "routed raw pack: adapter entries exceed their buffer");
+            }
+        }
     }
     if (s.raw_out) {  // a raw pack: its trimmed-adapter entries follow the output text
         fq_raw_out* o = s.raw_out;
@@ -739,6 +790,164 @@ int fq_engine_submit_text(fq_engine* e, const fq_text_batch* tb, fq_read_result*
     return FQ_OK;
 }
 
+// ---- routed egress ---------------------------------------------------------------------------
+
+// a FAILED record: its input plus a blank and the longest tag ("paired_read_is_failing", 22 bytes)
+static const size_t kFailedTag = 24;
+
+size_t fq_egress_bound(int32_t stream, uint64_t text_bytes1, uint64_t text_bytes2, uint64_t n) {
+    const bool pe = text_bytes2 != 0;
+    switch (stream) {
+        case FQ_EG_OUT1: case FQ_EG_UNPAIRED1: return (size_t)text_bytes1 + kTextSlack;
+        case FQ_EG_OUT2: case FQ_EG_UNPAIRED2: return (size_t)text_bytes2 + kTextSlack;
+        case FQ_EG_MERGED: return merged_cap(text_bytes1, text_bytes2, (size_t)n);
+        case FQ_EG_FAILED: return (size_t)text_bytes1 + (size_t)text_bytes2 + kFailedTag * (size_t)n * (pe ? 2 : 1) + kTextSlack;
+        default: return 0;
+    }
+}
+
+int fq_engine_set_egress(fq_engine* e, const fq_egress* eg) {
+    if (!e) return FQ_E_INVALID;
+    if (!e->pending.empty() || !e->raw_queued.empty()) return fail(e, FQ_E_INVALID, "fq_engine_set_egress with packs in flight");
+    if (eg && (eg->open >> FQ_EG_STREAMS)) return fail(e, FQ_E_INVALID, "fq_engine_set_egress: unknown stream bits");
+    if (e->raw) return fail(e, FQ_E_INVALID, "fq_engine_set_egress inside a raw stream");
+    for (Slot& s : e->slots) s.raw_ready = false;  // (raw slots carry the open streams' buffers)
+    e->eg_on = eg != nullptr;
+    e->eg_open = eg ? eg->open : 0;
+    return FQ_OK;
+}
+
+// the routed pack's per-stream device buffers (grown on demand, as ensure_text's)
+static int ensure_egress_caps(fq_engine* e, Slot& s, uint64_t text1, uint64_t text2, size_t n);
+static int ensure_egress(fq_engine* e, Slot& s, const fq_text_batch* tb) {
+    return ensure_egress_caps(e, s, tb->text_bytes[0], e->p.paired ? tb->text_bytes[1] : 0, (size_t)tb->n);
+}
+static int ensure_egress_caps(fq_engine* e, Slot& s, uint64_t text1, uint64_t text2, size_t n) {
+    if (!s.d_egtotal) HIP_TRY(e, hipMalloc(&s.d_egtotal, FQ_EG_STREAMS * sizeof(unsigned long long)));
+    if (!s.h_egtotal)
+        HIP_TRY(e, hipHostMalloc((void**)&s.h_egtotal, FQ_EG_STREAMS * sizeof(unsigned long long), hipHostMallocDefault));
+    const size_t recs = n + n / 8 + 1;
+    for (int k = 0; k < FQ_EG_STREAMS; ++k) {
+        if (!((e->eg_open >> k) & 1u)) continue;
+        if (n > s.eg_recs[k]) {
+            if (s.d_egsize[k]) (void)hipFree(s.d_egsize[k]);
+            if (s.d_egoff[k]) (void)hipFree(s.d_egoff[k]);
+            s.d_egsize[k] = s.d_egoff[k] = nullptr;
+            s.eg_recs[k] = 0;
+            HIP_TRY(e, hipMalloc(&s.d_egsize[k], recs * sizeof(uint32_t)));
+            HIP_TRY(e, hipMalloc(&s.d_egoff[k], recs * sizeof(uint32_t)));
+            s.eg_recs[k] = recs;
+        }
+        const size_t need = fq_egress_bound(k, text1, text2, (uint64_t)n);
+        if (need > s.eg_cap[k]) {
+            if (s.d_eg[k]) (void)hipFree(s.d_eg[k]);
+            s.d_eg[k] = nullptr;
+            s.eg_cap[k] = 0;
+            const size_t cap = need + need / 8;
+            HIP_TRY(e, hipMalloc(&s.d_eg[k], cap));
+            s.eg_cap[k] = cap;
+        }
+    }
+    return FQ_OK;
+}
+
+int fq_engine_submit_text_routed(fq_engine* e, const fq_text_batch* tb, fq_read_result* results, fq_egress_out* out,
+                                 uint64_t seq_no) {
+    if (!e || !tb || !results || !out) return FQ_E_INVALID;
+    const bool pe = e->p.paired;
+    const int mates = pe ? 2 : 1;
+    if (!e->eg_on) return fail(e, FQ_E_INVALID, "routed text pack without fq_engine_set_egress");
+    if (e->gz_level) return fail(e, FQ_E_INVALID, "routed text packs take no device BGZF output");
+    if (e->raw) return fail(e, FQ_E_INVALID, "routed text pack inside a raw stream");
+    if (tb->n < 0 || tb->n > e->max_batch || tb->stride <= 0 || tb->stride > e->max_stride || (tb->stride & 15))
+        return fail(e, FQ_E_INVALID, "text pack exceeds the engine's max_batch/max_stride (or stride % 16 != 0)");
+    if (e->p.umi_front1 > 0 || e->p.umi_front2 > 0) return fail(e, FQ_E_INVALID, "routed text packs take no UMI options");
+    if (e->p.correction_enabled && tb->stride > 32768)
+        return fail(e, FQ_E_INVALID, "-c takes reads of at most 32767 bases (the record's overlap offset is 16-bit)");
+    for (int m = 0; m < mates; ++m)
+        if (tb->n > 0 && (!tb->text[m] || !tb->rec[m])) return fail(e, FQ_E_INVALID, "missing text pack arrays");
+    // every open stream needs a buffer of at least its bound, before anything is launched or copied
+    for (int k = 0; k < FQ_EG_STREAMS; ++k) {
+        out->bytes[k] = 0;
+        if (!((e->eg_open >> k) & 1u)) continue;
+        const size_t need = fq_egress_bound(k, tb->text_bytes[0], pe ? tb->text_bytes[1] : 0, (uint64_t)tb->n);
+        if (!out->text[k] || out->cap[k] < need)
+            return fail(e, FQ_E_INVALID, "routed text pack: an open stream's buffer is missing or below fq_egress_bound");
+    }
+    if (tb->n == 0) {
+        e->pending.push_back(Pending{seq_no, -1, true, 0});
+        return FQ_OK;
+    }
+    HIP_TRY(e, hipSetDevice(e->device));
+    int k = 0;
+    for (auto it = e->pending.rbegin(); it != e->pending.rend(); ++it)
+        if (it->slot >= 0) {
+            k = (it->slot + 1) % kSlots;
+            break;
+        }
+    int rc = retire_slot(e, k);
+    if (rc != FQ_OK) return rc;
+    Slot& s = e->slots[k];
+    if ((rc = alloc_slot(e, s)) != FQ_OK) return rc;
+    if ((rc = ensure_text(e, s, tb)) != FQ_OK) return rc;
+    if ((rc = ensure_egress(e, s, tb)) != FQ_OK) return rc;
+    const size_t plane = fq_batch_bytes(e->max_batch, e->max_stride);
+    fq_batch db{};
+    db.n = tb->n;
+    db.stride = tb->stride;
+    db.seq1 = s.d_rows;
+    db.qual1 = s.d_rows + plane;
+    db.len1 = s.d_lens;
+    db.seq2 = pe ? s.d_rows + 2 * plane : nullptr;
+    db.qual2 = pe ? s.d_rows + 3 * plane : nullptr;
+    db.len2 = pe ? s.d_lens + e->max_batch : nullptr;
+    for (int m = 0; m < mates; ++m) {
+        HIP_TRY(e, hipMemcpyAsync(s.d_text[m], tb->text[m], tb->text_bytes[m], hipMemcpyHostToDevice, e->s_in));
+        HIP_TRY(e, hipMemcpyAsync(s.d_trec[m], tb->rec[m], (size_t)tb->n * sizeof(fq_text_rec), hipMemcpyHostToDevice,
+                                  e->s_in));
+    }
+    HIP_TRY(e, hipEventRecord(s.ev_in, e->s_in));
+    HIP_TRY(e, hipStreamWaitEvent(e->stream, s.ev_in, 0));
+    for (int m = 0; m < mates; ++m)
+        HIP_TRY(e, fq_launch_text_tiles(s.d_text[m], s.d_trec[m], tb->n, tb->stride, const_cast<uint8_t*>(m ? db.seq2 : db.seq1),
+                                        const_cast<uint8_t*>(m ? db.qual2 : db.qual1), const_cast<uint16_t*>(m ? db.len2 : db.len1),
+                                        e->stream));
+    HIP_TRY(e, hipMemsetAsync(s.d_err, 0, sizeof(int), e->stream));
+    if ((rc = launch(e, db, s.d_res, e->stream, s.scratch, false, false, seq_no, s.d_err)) != FQ_OK) return rc;
+    // the six streams: corrected pairs (-c, PE) read their rows back from the planes
+    fq_egress_args a{};
+    fq_egress_streams st{};
+    const bool planes = pe && e->p.correction_enabled;
+    for (int m = 0; m < mates; ++m) {
+        a.text[m] = s.d_text[m];
+        a.rec[m] = s.d_trec[m];
+        a.seq[m] = planes ? (m ? db.seq2 : db.seq1) : nullptr;
+        a.qual[m] = planes ? (m ? db.qual2 : db.qual1) : nullptr;
+    }
+    a.res = s.d_res;
+    a.n = tb->n, a.stride = tb->stride, a.paired = pe ? 1 : 0;
+    a.merge = pe && e->p.merge_enabled, a.discard = e->p.discard_unmerged;
+    a.open = e->eg_open;
+    for (int q = 0; q < FQ_EG_STREAMS; ++q) st.size[q] = s.d_egsize[q], st.off[q] = s.d_egoff[q], st.out[q] = s.d_eg[q];
+    st.total = s.d_egtotal;
+    HIP_TRY(e, fq_launch_egress(a, st, s.d_scan, s.scan_bytes, e->stream));
+    // records, sizes and the error word behind the kernels; each stream's text follows once the
+    // sizes are in (issue_copies)
+    const size_t nres = (size_t)tb->n * mates;
+    HIP_TRY(e, hipMemcpyAsync(results, s.d_res, nres * sizeof(fq_read_result), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(s.h_egtotal, s.d_egtotal, FQ_EG_STREAMS * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                              e->stream));
+    HIP_TRY(e, hipMemcpyAsync(s.h_err, s.d_err, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipEventRecord(s.ev_kern, e->stream));
+    s.copy_dst[0] = s.copy_dst[1] = nullptr;
+    s.copy_cap[0] = s.copy_cap[1] = 0;
+    s.copy_pending = true;
+    s.busy = true;
+    s.eg_out = out;
+    e->pending.push_back(Pending{seq_no, k, false, 0});
+    return issue_copies(e, -1);
+}
+
 // ---- raw FASTQ streams -----------------------------------------------------------------------
 
 // the raw-window buffers of slot s (the text-pack buffers at raw capacity plus the line index)
@@ -779,6 +988,12 @@ static int ensure_raw(fq_engine* e, Slot& s) {
         HIP_TRY(e, hipMalloc(&s.d_bbase[m], (size_t)e->raw_nblocks * sizeof(uint32_t)));
 
     }
+    if (e->eg_on) {  // routed raw packs: every open stream at the window's capacity, the entries apart
+        const int rc = ensure_egress_caps(e, s, text, pe ? text : 0, recs);
+        if (rc != FQ_OK) return rc;
+        for (int m = 0; m < (pe ? 2 : 1); ++m) HIP_TRY(e, hipMalloc(&s.d_ad[m], text + 3 * recs + 64));
+        s.ad_cap = text + 3 * recs + 64;
+    }
     s.text_cap[0] = s.text_cap[1] = 0;  // (not the text-pack sizes: ensure_text re-allocates)
     s.trec_cap = 0;
     if (s.d_scan) (void)hipFree(s.d_scan);
@@ -796,9 +1011,12 @@ static int ensure_raw(fq_engine* e, Slot& s) {
 int fq_engine_raw_begin(fq_engine* e, uint64_t window_cap, uint64_t carry_cap) {
     if (!e) return FQ_E_INVALID;
     if (!e->pending.empty() || !e->raw_queued.empty()) return fail(e, FQ_E_INVALID, "fq_engine_raw_begin with packs in flight");
-    if (e->p.correction_enabled || e->p.umi_front1 > 0 || e->p.umi_front2 > 0 ||
-        (e->p.merge_enabled && e->p.discard_unmerged))
+    // (-c and --discard_unmerged: only with an egress set, whose packs fq_engine_raw_launch_routed writes)
+    if (e->p.umi_front1 > 0 || e->p.umi_front2 > 0 ||
+        (!e->eg_on && (e->p.correction_enabled || (e->p.merge_enabled && e->p.discard_unmerged))))
         return fail(e, FQ_E_INVALID, "raw streams take no -c, UMI or --discard_unmerged options");
+    if (e->p.correction_enabled && e->max_stride > 32768)
+        return fail(e, FQ_E_INVALID, "-c takes reads of at most 32767 bases (the record's overlap offset is 16-bit)");
     const double tb = engine_timing() ? now_s() : 0;
     struct Stamp {
         double t;
@@ -910,6 +1128,9 @@ int fq_engine_raw_launch(fq_engine* e, fq_raw_result* r, fq_raw_out* out, uint64
     if (!e || !r || !out) return FQ_E_INVALID;
     if (e->raw_queued.empty()) return fail(e, FQ_E_INVALID, "fq_engine_raw_launch without an enqueued window");
     if (e->gz_level && out->results) return fail(e, FQ_E_INVALID, "raw pack: records-only egress while gz output is on");
+    // (its two streams cannot hold what -c and --discard_unmerged write: fq_engine_raw_launch_routed)
+    if (e->p.correction_enabled || (e->p.merge_enabled && e->p.discard_unmerged))
+        return fail(e, FQ_E_INVALID, "raw streams take no -c, UMI or --discard_unmerged options");
     HIP_TRY(e, hipSetDevice(e->device));
     const int k = e->raw_queued.front();
     e->raw_queued.pop_front();
@@ -995,6 +1216,93 @@ int fq_engine_raw_launch(fq_engine* e, fq_raw_result* r, fq_raw_out* out, uint64
     s.busy = true;
     s.text_out = &out->text;
     s.raw_out = out;
+    e->pending.push_back(Pending{seq_no, k, false, 0});
+    return issue_copies(e, -1);
+}
+
+int fq_engine_raw_launch_routed(fq_engine* e, fq_raw_result* r, fq_raw_egress_out* out, uint64_t seq_no) {
+    if (!e || !r || !out) return FQ_E_INVALID;
+    if (!e->eg_on) return fail(e, FQ_E_INVALID, "routed raw pack without fq_engine_set_egress");
+    if (e->gz_level) return fail(e, FQ_E_INVALID, "routed raw packs take no device BGZF output");
+    if (e->raw_queued.empty()) return fail(e, FQ_E_INVALID, "fq_engine_raw_launch_routed without an enqueued window");
+    HIP_TRY(e, hipSetDevice(e->device));
+    const int k = e->raw_queued.front();
+    Slot& s = e->slots[k];
+    HIP_TRY(e, hipEventSynchronize(s.ev_idx));  // (returns at once after fq_engine_raw_wait)
+    const bool pe = e->p.paired;
+    const int mates = pe ? 2 : 1;
+    raw_result_of(e, s, r);
+    const int n = r->pairs;
+    // every open stream (and, with -a, each mate's entries) needs a buffer of at least its bound; a
+    // refusal leaves the window enqueued
+    for (int q = 0; q < FQ_EG_STREAMS; ++q) {
+        out->eg.bytes[q] = 0;
+        if (!((e->eg_open >> q) & 1u) || n <= 0) continue;
+        const size_t need = fq_egress_bound(q, r->text_bytes[0], pe ? r->text_bytes[1] : 0, (uint64_t)n);
+        if (!out->eg.text[q] || out->eg.cap[q] < need)
+            return fail(e, FQ_E_INVALID, "routed raw pack: an open stream's buffer is missing or below fq_egress_bound");
+    }
+    for (int m = 0; m < 2; ++m) {
+        out->adapter_bytes[m] = 0;
+        if (m >= mates || n <= 0 || !e->p.adapter_trimming) continue;
+        if (!out->adapters[m] || out->adapter_cap[m] < (size_t)r->text_bytes[m] + 3 * (size_t)n + kTextSlack)
+            return fail(e, FQ_E_INVALID, "routed raw pack: an adapter-entry buffer is missing or too small");
+    }
+    e->raw_queued.pop_front();
+    if (n <= 0) {
+        e->pending.push_back(Pending{seq_no, -1, true, 0});
+        return FQ_OK;
+    }
+    const size_t plane = fq_batch_bytes(e->max_batch, e->max_stride);
+    fq_batch db{};
+    db.n = n;
+    db.stride = std::max(16, (r->max_len + 15) & ~15);
+    db.seq1 = s.d_rows;
+    db.qual1 = s.d_rows + plane;
+    db.len1 = s.d_lens;
+    db.seq2 = pe ? s.d_rows + 2 * plane : nullptr;
+    db.qual2 = pe ? s.d_rows + 3 * plane : nullptr;
+    db.len2 = pe ? s.d_lens + e->max_batch : nullptr;
+    HIP_TRY(e, hipStreamWaitEvent(e->stream, s.ev_idx, 0));
+    for (int m = 0; m < mates; ++m)
+        HIP_TRY(e, fq_launch_text_tiles(s.d_text[m], s.d_trec[m], n, db.stride, const_cast<uint8_t*>(m ? db.seq2 : db.seq1),
+                                        const_cast<uint8_t*>(m ? db.qual2 : db.qual1), const_cast<uint16_t*>(m ? db.len2 : db.len1),
+                                        e->stream));
+    HIP_TRY(e, hipMemsetAsync(s.d_err, 0, sizeof(int), e->stream));
+    int rc = launch(e, db, s.d_res, e->stream, s.scratch, false, false, seq_no, s.d_err);
+    if (rc != FQ_OK) return rc;
+    HIP_TRY(e, hipMemsetAsync(s.d_total, 0, 4 * sizeof(unsigned long long), e->stream));
+    fq_egress_args a{};
+    fq_egress_streams st{};
+    const bool planes = pe && e->p.correction_enabled;
+    for (int m = 0; m < mates; ++m) {
+        a.text[m] = s.d_text[m];
+        a.rec[m] = s.d_trec[m];
+        a.seq[m] = planes ? (m ? db.seq2 : db.seq1) : nullptr;
+        a.qual[m] = planes ? (m ? db.qual2 : db.qual1) : nullptr;
+    }
+    a.res = s.d_res;
+    a.n = n, a.stride = db.stride, a.paired = pe ? 1 : 0;
+    a.merge = pe && e->p.merge_enabled, a.discard = e->p.discard_unmerged;
+    a.open = e->eg_open;
+    for (int q = 0; q < FQ_EG_STREAMS; ++q) st.size[q] = s.d_egsize[q], st.off[q] = s.d_egoff[q], st.out[q] = s.d_eg[q];
+    st.total = s.d_egtotal;
+    HIP_TRY(e, fq_launch_egress(a, st, s.d_scan, s.scan_bytes, e->stream));
+    // the trimmed-adapter entries per mate, into their own buffer (corrected pairs: the corrected bytes)
+    for (int m = 0; m < mates && e->p.adapter_trimming; ++m)
+        HIP_TRY(e, fq_launch_egress_adapters(a, m, s.d_tsize[m], s.d_toff[m], s.d_scan, s.scan_bytes, s.d_ad[m],
+                                             (unsigned long long)s.ad_cap, s.d_total + 2 + m, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(s.h_egtotal, s.d_egtotal, FQ_EG_STREAMS * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                              e->stream));
+    HIP_TRY(e, hipMemcpyAsync(s.h_total, s.d_total, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(s.h_err, s.d_err, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipEventRecord(s.ev_kern, e->stream));
+    s.copy_dst[0] = s.copy_dst[1] = nullptr;
+    s.copy_cap[0] = s.copy_cap[1] = 0;
+    s.copy_pending = true;
+    s.busy = true;
+    s.eg_out = &out->eg;
+    s.reg_out = out;
     e->pending.push_back(Pending{seq_no, k, false, 0});
     return issue_copies(e, -1);
 }

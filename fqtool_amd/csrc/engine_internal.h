@@ -60,6 +60,31 @@ hipError_t fq_launch_merge_out(const char* d_text1, const char* d_text2, const f
                                const fq_text_rec* d_rec2, const fq_read_result* d_res, int n, int discard,
                                uint32_t* d_size, uint32_t* d_off, void* d_temp, size_t temp_bytes, char* d_out,
                                unsigned long long* d_total, hipStream_t s);
+// Routed egress of a text pack (text.hip, the per-pair routine of egress_core.h): every open stream's
+// output text, st.total[s] = its bytes (0 for a stream that is not open)
+struct fq_egress_args {
+    const char* text[2];
+    const fq_text_rec* rec[2];
+    const fq_read_result* res;
+    const uint8_t* seq[2];   // the tile planes when -c ran (corrected pairs are read from them), else null
+    const uint8_t* qual[2];
+    int n, stride, paired, merge, discard;
+    uint32_t open;
+};
+struct fq_egress_streams {
+    uint32_t* size[FQ_EG_STREAMS];  // n each, open streams only
+    uint32_t* off[FQ_EG_STREAMS];
+    char* out[FQ_EG_STREAMS];
+    unsigned long long* total;      // [FQ_EG_STREAMS]
+};
+hipError_t fq_launch_egress(const fq_egress_args& a, const fq_egress_streams& st, void* d_temp, size_t temp_bytes,
+                            hipStream_t s);
+// trimmed-adapter entries of mate m of a routed raw pack (the format of fq_launch_raw_adapters), from
+// d_out's start; a corrected pair's bytes come from the planes.  *d_total = their bytes, ~0 (nothing
+// written) if they exceed cap
+hipError_t fq_launch_egress_adapters(const fq_egress_args& a, int m, uint32_t* d_size, uint32_t* d_off, void* d_temp,
+                                     size_t temp_bytes, char* d_out, unsigned long long cap, unsigned long long* d_total,
+                                     hipStream_t s);
 // Device BGZF (deflate.hip): scratch of the compressor, shared by the launches of one stream (they
 // run one after another): a token array per resident workgroup, a 64 KiB slot and a size per member
 struct fq_deflate_scratch {

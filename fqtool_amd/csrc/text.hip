@@ -13,6 +13,7 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include "egress_core.h"
 #include "engine_internal.h"
 
 namespace {
@@ -103,40 +104,11 @@ __global__ void text_write_kernel(const char* __restrict__ text, const fq_text_r
 // "_merged_<m1>_<m2>" spliced in before the name's first space, r1[0, m1) + revcomp(r2[0, m2)),
 // qualities r1's then r2's reversed, read 1's strand line), else (unless --discard_unmerged) each
 // read that passes; nothing reaches out1 / out2.  One thread per pair.
-__device__ __forceinline__ int dec_digits(int v) {
-    int d = 1;
-    while (v >= 10) {
-        v /= 10;
-        ++d;
-    }
-    return d;
-}
-
-__device__ __forceinline__ char* put_dec(char* d, int v) {
-    const int nd = dec_digits(v);
-    for (int k = nd - 1; k >= 0; --k) {
-        d[k] = (char)('0' + v % 10);
-        v /= 10;
-    }
-    return d + nd;
-}
-
-// the name's first space (or -1)
-__device__ __forceinline__ int first_space(const char* s, int n) {
-    for (int k = 0; k < n; ++k)
-        if (s[k] == ' ') return k;
-    return -1;
-}
-
-__device__ __forceinline__ char comp_base(char c) {
-    switch (c) {
-        case 'A': case 'a': return 'T';
-        case 'T': case 't': return 'A';
-        case 'C': case 'c': return 'G';
-        case 'G': case 'g': return 'C';
-        default: return 'N';
-    }
-}
+// (the digits, the name's first space and the complement: egress_core.h's, shared with the routed egress)
+using fqegress::dec_digits;
+using fqegress::first_space;
+using fqegress::put_dec;
+__device__ __forceinline__ char comp_base(char c) { return fqegress::comp(c); }
 
 __device__ __forceinline__ uint32_t read_bytes(const fq_text_rec& R, const fq_read_result& r) {
     return (uint32_t)R.name_len + R.strand_len + 2u * r.len + 4u;
@@ -244,7 +216,121 @@ __global__ void merge_write_kernel(const char* __restrict__ text1, const char* _
     *d = '\n';
 }
 
+
+// ---- routed egress (fq_engine_set_egress): six streams, the per-pair routine of egress_core.h ----
+// One lane per pair: egress_size_kernel stores the bytes the pair adds to each open stream, one
+// exclusive scan per open stream turns them into the pair's cursors, egress_write_kernel writes.
+__global__ void egress_size_kernel(fqegress::Pack pk, fq_egress_streams st) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= pk.n) return;
+    fqegress::Mate m[2];
+    bool planes;
+    const fqegress::Plan p = fqegress::load(pk, i, m, planes);
+    uint32_t z[FQ_EG_STREAMS];
+    fqegress::sizes(p, m, z);
+#pragma unroll
+    for (int s = 0; s < FQ_EG_STREAMS; ++s)
+        if ((pk.open >> s) & 1u) st.size[s][i] = z[s];
+}
+
+__global__ void egress_total_kernel(fq_egress_streams st, uint32_t open, int n) {
+    const int s = threadIdx.x;
+    if (blockIdx.x || s >= FQ_EG_STREAMS) return;
+    st.total[s] = ((open >> s) & 1u) && n ? (unsigned long long)st.off[s][n - 1] + st.size[s][n - 1] : 0ull;
+}
+
+__global__ void egress_write_kernel(fqegress::Pack pk, fq_egress_streams st) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= pk.n) return;
+    fqegress::Mate m[2];
+    bool planes;
+    const fqegress::Plan p = fqegress::load(pk, i, m, planes);
+    if (!p.n) return;
+    char* d[FQ_EG_STREAMS];
+#pragma unroll
+    for (int s = 0; s < FQ_EG_STREAMS; ++s) d[s] = ((pk.open >> s) & 1u) ? st.out[s] + st.off[s][i] : nullptr;
+    fqegress::write(p, m, planes, d);
+}
+
+// trimmed-adapter entries of a routed raw pack (raw.hip's entry format, from the buffer's start): the
+// read's bytes come from the planes for a corrected pair, as the streams' do
+__global__ void egress_ad_size_kernel(fqegress::Pack pk, int m, uint32_t* __restrict__ size) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= pk.n) return;
+    const fq_read_result& r = pk.res[pk.paired ? 2 * (size_t)i + m : (size_t)i];
+    const bool has = (r.flags & (FQ_RF_AD_OVERLAP | FQ_RF_AD_SEQ)) && r.ad_len != 0;
+    size[i] = !has ? 0u : (r.flags & FQ_RF_AD_NEG) ? 5u : 3u + r.ad_len;
+}
+
+__global__ void egress_ad_write_kernel(fqegress::Pack pk, int m, const uint32_t* __restrict__ size,
+                                       const uint32_t* __restrict__ off, char* __restrict__ out, unsigned long long cap,
+                                       unsigned long long* __restrict__ total) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long end = (unsigned long long)off[pk.n - 1] + size[pk.n - 1];
+    if (i == pk.n - 1) *total = end <= cap ? end : ~0ull;
+    if (i >= pk.n || size[i] == 0 || end > cap) return;
+    fqegress::Mate mt[2];
+    bool planes;
+    fqegress::load(pk, i, mt, planes);
+    const fqegress::Mate& M = mt[pk.paired ? m : 0];
+    const fq_read_result& r = M.r;
+    char* d = out + off[i];
+    d[0] = (char)(r.ad_len & 0xFF);
+    d[1] = (char)(r.ad_len >> 8);
+    if (r.flags & FQ_RF_AD_NEG) {
+        d[2] = 1;
+        d[3] = (char)(r.ad_pos & 0xFF);
+        d[4] = (char)(r.ad_pos >> 8);
+        return;
+    }
+    d[2] = 0;
+    for (int b = 0; b < r.ad_len; ++b) d[3 + b] = fqegress::seq_at(M, planes, r.ad_pos + b);
+}
+
+static fqegress::Pack egress_pack(const fq_egress_args& a) {
+    fqegress::Pack pk{};
+    for (int m = 0; m < 2; ++m) pk.text[m] = a.text[m], pk.rec[m] = a.rec[m], pk.seq[m] = a.seq[m], pk.qual[m] = a.qual[m];
+    pk.res = a.res;
+    pk.n = a.n, pk.stride = a.stride, pk.paired = a.paired, pk.merge = a.merge, pk.discard = a.discard, pk.open = a.open;
+    return pk;
+}
+
 }  // namespace
+
+hipError_t fq_launch_egress_adapters(const fq_egress_args& a, int m, uint32_t* d_size, uint32_t* d_off, void* d_temp,
+                                     size_t temp_bytes, char* d_out, unsigned long long cap, unsigned long long* d_total,
+                                     hipStream_t s) {
+    if (a.n <= 0) return hipMemsetAsync(d_total, 0, sizeof(unsigned long long), s);
+    const fqegress::Pack pk = egress_pack(a);
+    const dim3 g((a.n + 255) / 256), b(256);
+    hipLaunchKernelGGL(egress_ad_size_kernel, g, b, 0, s, pk, m, d_size);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    size_t tb = temp_bytes;
+    e = hipcub::DeviceScan::ExclusiveSum(d_temp, tb, d_size, d_off, a.n, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(egress_ad_write_kernel, g, b, 0, s, pk, m, d_size, d_off, d_out, cap, d_total);
+    return hipGetLastError();
+}
+
+hipError_t fq_launch_egress(const fq_egress_args& a, const fq_egress_streams& st, void* d_temp, size_t temp_bytes,
+                            hipStream_t s) {
+    if (a.n <= 0) return hipMemsetAsync(st.total, 0, FQ_EG_STREAMS * sizeof(unsigned long long), s);
+    const fqegress::Pack pk = egress_pack(a);
+    const dim3 g((a.n + 255) / 256), b(256);
+    hipLaunchKernelGGL(egress_size_kernel, g, b, 0, s, pk, st);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    for (int k = 0; k < FQ_EG_STREAMS; ++k) {
+        if (!((a.open >> k) & 1u)) continue;
+        size_t tb = temp_bytes;
+        e = hipcub::DeviceScan::ExclusiveSum(d_temp, tb, st.size[k], st.off[k], a.n, s);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(egress_total_kernel, dim3(1), dim3(64), 0, s, st, a.open, a.n);
+    hipLaunchKernelGGL(egress_write_kernel, g, b, 0, s, pk, st);
+    return hipGetLastError();
+}
 
 hipError_t fq_launch_merge_out(const char* d_text1, const char* d_text2, const fq_text_rec* d_rec1,
                                const fq_text_rec* d_rec2, const fq_read_result* d_res, int n, int discard,

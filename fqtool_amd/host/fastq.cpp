@@ -1312,6 +1312,7 @@ void Pool::run(int n, const std::function<void(int)>& fn) {
 void Pack::clear() {
     n = 0;
     raw = false;
+    routed = false;
     gz_members = false;
     recs = false;
     zc = false;

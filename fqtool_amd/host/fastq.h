@@ -267,7 +267,8 @@ struct Pack {
           flags(pinned),
           res(pinned),
           trec{PodBuf<fq_text_rec>(pinned), PodBuf<fq_text_rec>(pinned)},
-          out_text{ByteBuf(pinned), ByteBuf(pinned)} {}
+          out_text{ByteBuf(pinned), ByteBuf(pinned)},
+          eg_text{ByteBuf(pinned), ByteBuf(pinned), ByteBuf(pinned), ByteBuf(false), ByteBuf(false), ByteBuf(false)} {}
     int n = 0;
     int stride = 0;
     bool paired = false;
@@ -292,6 +293,15 @@ struct Pack {
     ByteBuf out_text[2];
     fq_text_out tout{};
     int max_len[2] = {0, 0};
+    // routed egress (fq_engine_submit_text_routed): the engine wrote every output stream of the
+    // pack, eg_text[s] / eout.bytes[s] for the streams that have a writer.  The pair and merged
+    // streams are page-locked; the unpaired and failed ones, which must hold their bound
+    // (fq_egress_bound: up to twice the input for FAILED) but usually receive a few percent of it,
+    // are ordinary memory: page-locking them cost more than their copies take
+    bool routed = false;
+    ByteBuf eg_text[FQ_EG_STREAMS];
+    fq_egress_out eout{};
+    fq_raw_egress_out reout{};  // a routed raw pack's descriptor (its entries land in text[m]); eout = reout.eg once reported
 
     // raw-stream pack (fq_engine_raw_*): the engine cut the records from the input bytes; its
     // trimmed-adapter entries follow the output text in out_text[m]; its staging window is recycled

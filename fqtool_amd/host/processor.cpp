@@ -31,6 +31,12 @@
 // the test builds) links all the same, and the tool then compresses on the host as before.
 #pragma weak fq_engine_set_gz_out
 #pragma weak fq_deflate_bound
+// The routed egress (-c, failed / unpaired outputs, -m --discard_unmerged on text packs) likewise:
+// without it those runs keep the host packs
+#pragma weak fq_engine_set_egress
+#pragma weak fq_egress_bound
+#pragma weak fq_engine_submit_text_routed
+#pragma weak fq_engine_raw_launch_routed
 // The k-mer statistics (--kmer --kmer_length) are bound weakly too; without them such a run fails
 // with a message instead of leaving the KmerCount sections out.
 #pragma weak fq_kstat_create
@@ -724,6 +730,43 @@ void OutputSet::write_merged_text(const char* t, size_t n, std::function<void()>
     wm_->write_raw(t, n, std::move(done), members);
 }
 
+uint32_t OutputSet::egress_mask() const {
+    uint32_t m = 0;
+    if (w1_ && (!paired_ || w2_)) m |= 1u << FQ_EG_OUT1 | (w2_ ? 1u << FQ_EG_OUT2 : 0u);
+    if (wm_) m |= 1u << FQ_EG_MERGED;
+    if (wu1_) m |= 1u << FQ_EG_UNPAIRED1;
+    if (wu2_) m |= 1u << FQ_EG_UNPAIRED2;
+    if (wf_) m |= 1u << FQ_EG_FAILED;
+    return m;
+}
+
+void OutputSet::write_routed(const fq_egress_out& out, std::function<void()> done) {
+    AsyncWriter* w[FQ_EG_STREAMS] = {};
+    const uint32_t mask = egress_mask();
+    w[FQ_EG_OUT1] = w1_.get(), w[FQ_EG_OUT2] = w2_.get(), w[FQ_EG_MERGED] = wm_.get();
+    w[FQ_EG_UNPAIRED1] = wu1_.get(), w[FQ_EG_UNPAIRED2] = wu2_.get(), w[FQ_EG_FAILED] = wf_.get();
+    int count = 0;
+    for (int s = 0; s < FQ_EG_STREAMS; ++s) count += (mask >> s) & 1u;
+    if (!count) {
+        done();
+        return;
+    }
+    auto left = std::make_shared<std::atomic<int>>(count);
+    auto fin = [left, done] {
+        if (left->fetch_sub(1) == 1) done();
+    };
+    std::exception_ptr err;
+    for (int s = 0; s < FQ_EG_STREAMS; ++s) {
+        if (!((mask >> s) & 1u)) continue;
+        try {
+            w[s]->write_raw(out.text[s], (size_t)out.bytes[s], fin, false);
+        } catch (...) {  // (write_raw has called fin before it throws, so the count still reaches zero)
+            if (!err) err = std::current_exception();
+        }
+    }
+    if (err) std::rethrow_exception(err);
+}
+
 void OutputSet::close() {
     std::exception_ptr first;
     for (auto* w : {&w1_, &w2_, &wu1_, &wu2_, &wf_, &wm_}) {
@@ -927,9 +970,12 @@ void Sink::consume(const Pack& pk, const fq_read_result* res) {
 
 bool Sink::plain_pair_outputs() const { return outs_ && !merge_ && outs_->plain_pair_outputs(); }
 
+uint32_t Sink::egress_mask() const { return outs_ ? outs_->egress_mask() : 0u; }
+
 void Sink::consume_text(const Pack& pk, std::function<void()> done) {
     pairs_ += (uint64_t)pk.n;
-    if (pk.zc) outs_->write_text_segs(pk.segs[0], pk.segs[1], std::move(done));
+    if (pk.routed) outs_->write_routed(pk.eout, std::move(done));
+    else if (pk.zc) outs_->write_text_segs(pk.segs[0], pk.segs[1], std::move(done));
     else if (merge_) outs_->write_merged_text(pk.out_text[0].data(), pk.tout.bytes[0], std::move(done), pk.gz_members);
     else
         outs_->write_text(pk.out_text[0].data(), pk.tout.bytes[0], pk.out_text[1].data(), pk.tout.bytes[1], std::move(done),
@@ -1387,6 +1433,8 @@ struct Lane {
     fq_dup* dup = nullptr;  // -d: this engine's table, kept across re-creation
     fq_kstat* kstat = nullptr;  // --kmer: this engine's k-mer tables, kept likewise
     int gz_level = 0;       // FQ_GZ_DEVICE=1 with .gz outputs: text / raw packs come back as BGZF members
+    bool routed = false;    // routed egress: text packs come back as the Sink's writers' streams
+    uint32_t eg_open = 0;   // ... those writers, as FQ_EG_* bits
     // an output buffer of x bytes of text, sized for its members instead
     size_t out_cap(size_t x) const { return gz_level ? fq_deflate_bound(x) : x; }
     int max_cycles = 0, max_batch = 0, max_stride = 0;
@@ -1421,6 +1469,11 @@ struct Lane {
         }
         if (gz_level && fq_engine_set_gz_out(e, gz_level) != FQ_OK)
             throw std::runtime_error(std::string("fq_engine_set_gz_out: ") + fq_engine_last_error(e));
+        if (routed) {
+            const fq_egress eg{eg_open, 0};
+            if (fq_engine_set_egress(e, &eg) != FQ_OK)
+                throw std::runtime_error(std::string("fq_engine_set_egress: ") + fq_engine_last_error(e));
+        }
         max_cycles = cycles;
         max_batch = batch;
         max_stride = stride;
@@ -1451,6 +1504,7 @@ struct Lane {
             if (pk->stage >= 0 && !pk->recs) (multi ? multi->free_stages : free_stages).push(pk->stage);
             if (!pk->recs) pk->stage = -1;
             pk->tout = pk->rout.text;
+            if (pk->routed) pk->eout = pk->reout.eg;
         }
         if (!out.push(std::move(pk))) throw Stopped();
         return true;
@@ -1466,6 +1520,21 @@ struct Lane {
                 tb.text[m] = pk.span[m];
                 tb.text_bytes[m] = pk.span_bytes[m];
                 tb.rec[m] = pk.trec[m].data();
+            }
+            if (routed) {  // every stream that has a writer, in a buffer of its bound (Pack::eg_text)
+                pk.routed = true;
+                pk.eout = fq_egress_out{};
+                for (int s = 0; s < FQ_EG_STREAMS; ++s) {
+                    if (!((eg_open >> s) & 1u)) continue;
+                    const size_t cap = fq_egress_bound(s, pk.span_bytes[0], pk.paired ? pk.span_bytes[1] : 0, (uint64_t)pk.n);
+                    pk.eg_text[s].resize_uninit(cap);
+                    pk.eout.text[s] = pk.eg_text[s].data();
+                    pk.eout.cap[s] = cap;
+                }
+                if (fq_engine_submit_text_routed(e, &tb, pk.results(), &pk.eout, pk.seq_no) != FQ_OK)
+                    throw std::runtime_error(std::string("fq_engine_submit_text_routed: ") + fq_engine_last_error(e));
+                submit_s += since(e0);
+                return;
             }
             if (gz_level) {  // (room for the members of the output text)
                 for (int m = 0; m < (pk.paired ? 2 : 1); ++m)
@@ -1563,7 +1632,7 @@ struct Lane {
         // the formatter writes the output from the staging window, which then keeps the carry
         // capacity free in front of the window bytes (the device buffer's layout)
         const char* eg_env = std::getenv("FQ_RAW_EGRESS");
-        const bool recs = !merge && !gz_level && eg_env && std::string(eg_env) == "host";
+        const bool recs = !merge && !gz_level && !routed && eg_env && std::string(eg_env) == "host";
         const uint64_t off0 = recs ? ccap : 0;
         const int raw_depth = 4;  // packs launched and not yet polled
         const size_t raw_ahead = 3;  // windows enqueued ahead of their launch (the copy-in queue)
@@ -1806,6 +1875,26 @@ struct Lane {
                             pk->rout.rec[m] = m < mates ? pk->trec[m].data() : nullptr;
                             pk->rout.text.text[m] = nullptr;
                         }
+                    } else if (routed) {  // every open stream at its bound over the window; the entries apart
+                        pk->routed = true;
+                        pk->reout = fq_raw_egress_out{};
+                        const uint64_t t1 = cin[0] + w.n[0], t2 = mates == 2 ? cin[1] + w.n[1] : 0;
+                        for (int s = 0; s < FQ_EG_STREAMS; ++s) {
+                            if (!((eg_open >> s) & 1u)) continue;
+                            const size_t cap = fq_egress_bound(s, t1, t2, (uint64_t)target);
+                            pk->eg_text[s].reserve(cap + cap / 8);
+                            pk->eg_text[s].resize_uninit(cap);
+                            pk->reout.eg.text[s] = pk->eg_text[s].data();
+                            pk->reout.eg.cap[s] = cap;
+                        }
+                        // (the entries' worst case is the whole input, their usual size a few percent of
+                        // it: ordinary memory, Pack::text, which a raw pack does not use otherwise)
+                        for (int m = 0; m < mates; ++m) {
+                            const size_t cap = (size_t)(cin[m] + w.n[m] + 3 * (uint64_t)target + 64);
+                            pk->text[m].resize_uninit(cap);
+                            pk->reout.adapters[m] = pk->text[m].data();
+                            pk->reout.adapter_cap[m] = cap;
+                        }
                     } else {
                         for (int m = 0; m < 2; ++m) {  // (output text, then the adapter entries)
                             size_t cap = m < mates ? (size_t)(cin[m] + w.n[m] + 4 * (uint64_t)target + 64) : 0;
@@ -1822,7 +1911,10 @@ struct Lane {
                     }
                     fq_raw_result r{};
                     const auto e0 = std::chrono::steady_clock::now();
-                    if (fq_engine_raw_launch(e, &r, &pk->rout, seq) != FQ_OK)
+                    if (routed) {
+                        if (fq_engine_raw_launch_routed(e, &r, &pk->reout, seq) != FQ_OK)
+                            throw std::runtime_error(std::string("fq_engine_raw_launch_routed: ") + fq_engine_last_error(e));
+                    } else if (fq_engine_raw_launch(e, &r, &pk->rout, seq) != FQ_OK)
                         throw std::runtime_error(std::string("fq_engine_raw_launch: ") + fq_engine_last_error(e));
                     submit_s += since(e0);
                     if (first_submit < 0) first_submit = since(t_start);
@@ -2344,11 +2436,24 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
         const char* tm_env = std::getenv("FQ_TEXT_MODE");
         // (-m: every pair's output goes to the merged stream, which the engine writes as well;
         // with --discard_unmerged the unmerged pairs go to out1 / out2 instead: host packs)
-        const bool text_mode = !(tm_env && std::string(tm_env) == "0") && !o.correction && !o.umi &&
-                               !o.index_filter && !o.split() && !o.phred64 && o.failed_out.empty() &&
-                               o.unpaired1.empty() && o.unpaired2.empty() &&
-                               (o.merge ? paired && !o.merge_out.empty() && !o.discard_unmerged
+        // Routed egress (fq_engine_set_egress, bound weakly): text packs whose six output streams the
+        // engine writes take -c, --failed_out, --unpaired_read1 (alone, or with --unpaired_read2 naming
+        // another file) and -m --discard_unmerged with out1 / out2 as well.  The combinations the
+        // golden fixtures do not pin keep the host packs: --unpaired_read2 alone or naming read 1's
+        // file, and -m together with the failed / unpaired outputs.
+        const bool eg_wanted = o.correction || !o.failed_out.empty() || !o.unpaired1.empty() || !o.unpaired2.empty() ||
+                               (o.merge && o.discard_unmerged);
+        const bool eg_side = !o.failed_out.empty() || !o.unpaired1.empty() || !o.unpaired2.empty();
+        const bool eg_unpaired_ok = o.unpaired2.empty() || (!o.unpaired1.empty() && o.unpaired1 != o.unpaired2);
+        const bool eg_ok = fq_engine_set_egress && fq_egress_bound && fq_engine_submit_text_routed && eg_unpaired_ok &&
+                           !(o.merge && eg_side) && (!(o.merge && o.discard_unmerged) || (!o.out1.empty() && !o.out2.empty()));
+        const bool text_mode = !(tm_env && std::string(tm_env) == "0") && (!eg_wanted || eg_ok) && !o.umi &&
+                               !o.index_filter && !o.split() && !o.phred64 &&
+                               (o.merge ? paired && !o.merge_out.empty()
                                         : !o.out1.empty() && (!paired || !o.out2.empty()));
+        // (the records-only egress and device BGZF stay with the plain pair / merged outputs)
+        const bool routed = text_mode && eg_wanted;
+        const uint32_t outs_mask = outs.egress_mask();  // (for the closing log line: the Sink is closed by then)
         // records-only raw packs to plain outputs go out as byte ranges of their windows (zero copy)
         const char* zc_env = std::getenv("FQ_RAW_ZC");  // (profiling: 0 formats every record)
         const bool zc_ok = outs.plain_pair_outputs() && !(zc_env && std::string(zc_env) == "0");
@@ -2369,7 +2474,9 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
         // single-stream gzip inputs for the raw stream: their inflaters start before the engines
         // are made (HIP start-up and the engines' allocations take ~0.1 s), not at the first window
         std::unique_ptr<ParGzSource> pre_gz[2];
-        if (text_mode && !o.interleaved && !(raw_env && std::string(raw_env) == "0") && gz_both && G == 1) {
+        // (routed runs take the raw stream on one engine; several engines share them out as text packs)
+        const bool raw_ok = !routed || (fq_engine_raw_launch_routed && G == 1);
+        if (text_mode && raw_ok && !o.interleaved && !(raw_env && std::string(raw_env) == "0") && gz_both && G == 1) {
             const std::string files[2] = {o.in1, o.in2};
             for (int m = 0; m < (paired ? 2 : 1); ++m)
                 // (a BGZF chain goes through the bulk reader's member inflater, never through this one)
@@ -2381,13 +2488,15 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
         // the call, keep the host's compression
         const char* gzd_env = std::getenv("FQ_GZ_DEVICE");
         const bool gz_device = gzd_env && std::string(gzd_env) == "1" && fq_engine_set_gz_out && fq_deflate_bound &&
-                               text_mode && o.compression >= 1 && o.compression <= 9 &&
+                               text_mode && !routed && o.compression >= 1 && o.compression <= 9 &&
                                (o.merge ? ends_with_gz(o.merge_out) : ends_with_gz(o.out1) && (!paired || ends_with_gz(o.out2)));
         for (int g = 0; g < G; ++g) {
             lanes.emplace_back(new Lane(devices[(size_t)g], depth));
             lanes.back()->gz_level = gz_device ? o.compression : 0;
             lanes.back()->t_start = t0;
             lanes.back()->merge = o.merge && paired;
+            lanes.back()->routed = routed;
+            lanes.back()->eg_open = routed ? outs.egress_mask() : 0u;
             lanes.back()->make(o, cyc0, (int)pack_n, stride0);
         }
         const double engines_ready_s = since(t0);
@@ -2411,7 +2520,7 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
         // dispatcher drives the raw stream first; the host reader takes over only where it stops
         // (single-stream gzip inputs on one engine too: their streams come from the parallel
         // inflater -- RawMulti reads windows with pread, plain files only)
-        const bool raw_mode = text_mode && !o.interleaved && !(raw_env && std::string(raw_env) == "0") &&
+        const bool raw_mode = text_mode && raw_ok && !o.interleaved && !(raw_env && std::string(raw_env) == "0") &&
                               ((!ends_with_gz(o.in1) && (!paired || !ends_with_gz(o.in2)) && pr.mapped()) ||
                                (gz_both && G == 1 && pr.parallel_gz()));
         std::promise<Lane::RawResume> raw_p;
@@ -2561,11 +2670,17 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
                     }
                     if (pk->text_mode) {  // the engine wrote the output text
                         if (o.adapter_trimming) {
-                            if (pk->raw)
+                            if (pk->raw && pk->routed)  // (the entries have buffers of their own)
+                                for (int m = 0; m < (paired ? 2 : 1); ++m)
+                                    ac.add_entries(m, pk->text[m].data(), pk->reout.adapter_bytes[m], p, &pool);
+                            else if (pk->raw)
                                 for (int m = 0; m < (paired ? 2 : 1); ++m)
                                     ac.add_entries(m, pk->out_text[m].data() + pk->tout.bytes[m], pk->rout.adapter_bytes[m], p, &pool);
-                            else
+                            else {
+                                // (-c: the recorded adapter strings are the corrected reads' bytes)
+                                if (pk->routed) apply_corrections(o, *pk, pk->res.data(), &pool);
                                 ac.add(*pk, pk->res.data(), p, &pool);
+                            }
                         }
                         format_s += since(f0);
                         reads += (uint64_t)pk->n * (paired ? 2 : 1);
@@ -2677,7 +2792,10 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
                             std::to_string(lanes[0]->raw_ready_wait_s) + " s, for a pack " + std::to_string(lanes[0]->raw_pack_wait_s) +
                             " s, in enqueue " + std::to_string(lanes[0]->raw_enqueue_s) + " s" +
                             (recs_packs ? "; records-only egress: " + std::to_string(recs_packs) + " packs, " + std::to_string(zc_packs) +
-                                              " as byte ranges of their windows" : std::string()) + ")"
+                                              " as byte ranges of their windows" : std::string()) +
+                            (routed ? "; routed egress of " + std::to_string(__builtin_popcount(outs_mask)) + " output streams" : std::string()) + ")"
+                      : routed    ? " (text packs: GPU ingest, routed egress of " + std::to_string(__builtin_popcount(outs_mask)) +
+                                        " output streams)"
                       : text_mode ? " (text packs: GPU ingest/egress)" : "") + ", wall " +
             std::to_string(since(t0)) + " s, engine submit " + std::to_string(submit_s) + " s, wait " + std::to_string(wait_s) + " s; pre-pass " +
             std::to_string(prepass_s) + " s, adapter detection (concurrent) " + std::to_string(detect_s) + " s, format " + std::to_string(format_s) + " s, parse " + std::to_string(parse_s) +

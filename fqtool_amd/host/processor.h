@@ -43,6 +43,11 @@ class OutputSet {
     bool plain_pair_outputs() const;  // out1 / out2 (those that exist) are not gzip
     // -m: a text pack's merged stream (the merged output; out1 / out2 get nothing)
     void write_merged_text(const char* t, size_t n, std::function<void()> done, bool members = false);
+    // routed egress (fq_engine_set_egress): the streams that have a writer, as FQ_EG_* bits (a
+    // paired run writes the pair outputs only with both writers), and a routed pack's streams handed
+    // to them; `done` runs once every writer is through with its text
+    uint32_t egress_mask() const;
+    void write_routed(const fq_egress_out& out, std::function<void()> done);
     void close();  // flushes and closes every file
 
    private:
@@ -70,6 +75,7 @@ class Sink {
     // the pack's text is written
     void consume_text(const Pack& pk, std::function<void()> done);
     bool plain_pair_outputs() const;  // text packs may go out as byte ranges (Pack::zc)
+    uint32_t egress_mask() const;     // the writers as FQ_EG_* bits (0 with -s / -S: no routed egress)
     void close();
 
    private:

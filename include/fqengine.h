@@ -361,7 +361,9 @@ int fq_engine_pending(const fq_engine* e); /* packs submitted and not yet report
  * out->text[0] (which must then hold text_bytes[0] + text_bytes[1] + 24 * n + 16 bytes), and
  * out->bytes[1] is 0.  Only for options whose outputs are out1 (+ out2) or that merged stream: no
  * -c, UMI, index filter, phred64, split, failed or unpaired outputs, no --discard_unmerged; the
- * host routes everything else through fq_engine_submit.  Records and text must stay valid until fq_engine_poll reports the pack; then
+ * routed egress below (fq_engine_set_egress, fq_engine_submit_text_routed) writes -c, failed,
+ * unpaired and --discard_unmerged runs' streams, and the host routes everything else through
+ * fq_engine_submit.  Records and text must stay valid until fq_engine_poll reports the pack; then
  * `results` holds the records as from fq_engine_submit and out->bytes[m] the bytes of out->text[m].
  * out->text[m] must hold at least the mate's text_bytes + 16 (a record's output is never longer
  * than its input text, except by the final line terminator that the input may lack). */
@@ -409,7 +411,8 @@ int fq_engine_submit_text(fq_engine* e, const fq_text_batch* tb, fq_read_result*
  * launched or not yet polled: a ninth enqueue waits for the oldest pack's copies); a window's
  * host bytes must stay valid until its pack is reported by fq_engine_poll.  Options as for text
  * packs (-m writes the merged stream into out->text.text[0], which must then hold both mates' window
- * and carry bytes + 28 * max_batch + 64; no -c, UMI, index filter, --discard_unmerged).
+ * and carry bytes + 28 * max_batch + 64; no -c, UMI, index filter, --discard_unmerged: those go
+ * through fq_engine_raw_launch_routed below).
  * The trimmed-adapter strings (FilterResult::addAdapterTrimmed, src/filterresult.cpp:138-157) come
  * back after the output text, at out->text.text[m] + out->text.bytes[m], adapter_bytes[m] bytes of
  * entries "u16 ad_len (little endian), u8 neg, then ad_len bytes of the read (neg 0) or u16
@@ -592,6 +595,71 @@ int fq_deflate_destroy(fq_deflate* d);
 int fq_deflate_bgzf(fq_deflate* d, const void* text, size_t n, int32_t level,
                     void* out, size_t out_cap, size_t* out_bytes);     /* host pointers, synchronous */
 int fq_engine_set_gz_out(fq_engine* e, int32_t level);                  /* 0 (default): off */
+
+/* ---- routed egress: every output stream of a text pack written on the GPU -----------------------
+ * The text packs above write out1 / out2 or the merged stream only.  An engine with an egress set
+ * routes each pair of a text pack as the loop bodies do (src/peprocessor.cpp:351-429,
+ * src/seprocessor.cpp:337-350; fqtool_amd/host/processor.cpp format_range) over six streams:
+ *   single end: a passing read -> OUT1; any other -> FAILED, tagged with its failure
+ *     (" failed_too_short" ... after the name, Read::toStringWithTag, src/read.h:170-178);
+ *   paired end: index-filtered pairs write nothing; with -m a merged pair that passes -> MERGED
+ *     (a merged pair that fails writes nothing) and, without --discard_unmerged, an unmerged pair's
+ *     passing reads -> MERGED; every other pair: both pass -> OUT1 and OUT2; only read 1 passes ->
+ *     with UNPAIRED1 open r1 -> UNPAIRED1 and r2 -> FAILED, else r1 -> FAILED tagged
+ *     "paired_read_is_failing" and r2 -> FAILED; only read 2 passes -> with UNPAIRED1 open (the
+ *     reference tests the left writer, src/peprocessor.cpp:417) r2 -> UNPAIRED2 and r1 -> FAILED
+ *     tagged with read 2's code (:420), else r1 -> FAILED and r2 -> FAILED tagged
+ *     "paired_read_is_failing".  FAILED holds both mates in pair order.
+ * A read is its record's window, or the whole read when its record is FQ_RF_NULL.  A stream whose
+ * bit is clear in fq_egress.open has no writer: what is routed there is dropped, and UNPAIRED1's bit
+ * is the "left writer" of the rules above.  With an egress set, fq_engine_submit_text_routed also
+ * takes -c (a pair with FQ_RF_CORRECTED on either record takes its sequence and quality bytes, the
+ * merged read's included, from the corrected rows of the tile planes; names and strand lines always
+ * come from the text) and -m --discard_unmerged; UMI is still refused.
+ * fq_engine_set_egress (only while no pack is pending or enqueued, else FQ_E_INVALID): NULL (the
+ * default) turns the routed egress off; fq_engine_submit_text, fq_engine_raw_begin and
+ * fq_engine_raw_launch write and refuse as before (fq_engine_raw_begin takes -c and
+ * --discard_unmerged once an egress is set, for fq_engine_raw_launch_routed below), and the routed
+ * calls are refused (FQ_E_INVALID) while no egress is set or device BGZF (fq_engine_set_gz_out) is on.
+ * fq_egress_bound (no device needed) is the capacity stream s needs for a pack of n records whose
+ * mates span text_bytes1 / text_bytes2 (0 for single end) bytes of input text: a record's output is
+ * its input (plus the final line terminator an input may lack); a FAILED record adds a blank and a
+ * tag of at most 23 bytes; MERGED is both mates' text plus a merged name's tag per pair, as for the
+ * text packs above.  fq_engine_submit_text_routed refuses (FQ_E_INVALID, before anything is launched
+ * or copied) an open stream without a buffer or with cap[s] below that bound.  The copies back are
+ * the exact byte counts: the sizes come back first, then each stream's text; bytes[s] is set when
+ * fq_engine_poll reports the pack (0 for a stream that is not open). */
+enum { FQ_EG_OUT1 = 0, FQ_EG_OUT2 = 1, FQ_EG_MERGED = 2, FQ_EG_UNPAIRED1 = 3, FQ_EG_UNPAIRED2 = 4, FQ_EG_FAILED = 5,
+       FQ_EG_STREAMS = 6 };
+typedef struct fq_egress {
+    uint32_t open;      /* bit s set: stream s has a writer */
+    uint32_t reserved;  /* 0 */
+} fq_egress;
+typedef struct fq_egress_out {
+    char* text[FQ_EG_STREAMS];     /* host buffers (pinned for full speed) of the open streams */
+    uint64_t cap[FQ_EG_STREAMS];   /* their capacities, >= fq_egress_bound */
+    uint64_t bytes[FQ_EG_STREAMS]; /* set when the pack is reported by fq_engine_poll */
+} fq_egress_out;
+size_t fq_egress_bound(int32_t stream, uint64_t text_bytes1, uint64_t text_bytes2, uint64_t n);
+int fq_engine_set_egress(fq_engine* e, const fq_egress* eg);
+int fq_engine_submit_text_routed(fq_engine* e, const fq_text_batch* tb, fq_read_result* results, fq_egress_out* out,
+                                 uint64_t seq_no);
+/* The same through the raw stream.  With an egress set, fq_engine_raw_begin also takes -c and
+ * -m --discard_unmerged, and each window's pack is launched with fq_engine_raw_launch_routed in
+ * fq_engine_raw_launch's place (which keeps refusing those options): the six streams as above, the
+ * bounds taken over the pack's fq_raw_result.text_bytes and pairs (the window's and carry's bytes
+ * and max_batch bound them before the launch), and the trimmed-adapter entries per mate, in
+ * fq_engine_raw_launch's entry format, in buffers of their own: adapters[m] of at least
+ * text_bytes[m] + 3 * pairs + 16 bytes when adapter_trimming is on; a corrected pair's entry holds
+ * the corrected bytes.  A refusal (FQ_E_INVALID: a missing or small buffer) comes before anything is
+ * launched and leaves the window enqueued.  fq_engine_set_egress is refused inside a raw stream. */
+typedef struct fq_raw_egress_out {
+    fq_egress_out eg;
+    char* adapters[2];         /* mate m's entries (adapters[1]: PE only) */
+    uint64_t adapter_cap[2];
+    uint64_t adapter_bytes[2]; /* set when the pack is reported by fq_engine_poll */
+} fq_raw_egress_out;
+int fq_engine_raw_launch_routed(fq_engine* e, fq_raw_result* r, fq_raw_egress_out* out, uint64_t seq_no);
 
 /* ---- device inflate: BGZF input members inflated on the GPU ---------------------------------------
  * The mirror of device BGZF.  Every BGZF member is an independent raw deflate stream (RFC 1951)

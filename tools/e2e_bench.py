@@ -170,6 +170,8 @@ def main():
     ap.add_argument("--null-out", action="store_true", help="FASTQ outputs to /dev/null (as bench.py's e2e leg)")
     ap.add_argument("--workers-list", default=None, help="comma list of -w values to run (overrides --workers)")
     ap.add_argument("--pause", type=float, default=0.0, help="seconds between fqtool-amd runs")
+    ap.add_argument("--tools", default=None, help="comma list of name=path binaries run in turn for every variant and "
+                    "repeat (A/B against another build; default: this tree's fqtool)")
     ap.add_argument("--gz", default=None, choices=["bgzf", "gzip"], help="compressed inputs: BGZF or one gzip stream")
     args = ap.parse_args()
     tmp = tempfile.mkdtemp(prefix="fqe2e_")
@@ -188,12 +190,13 @@ def main():
         ours = os.path.join(REPO, "fqtool_amd", "bin", "fqtool")
         variants = args.variants.split(";") if args.variants else [args.extra]
         wl = [int(x) for x in args.workers_list.split(",")] if args.workers_list else [args.workers]
-        for _, w, v in [(r, w, v) for v in variants for w in wl for r in range(args.repeat)]:
+        tools = [t.split("=", 1) for t in args.tools.split(",")] if args.tools else [["fqtool-amd", ours]]
+        for _, w, v, (name, binary) in [(r, w, v, t) for v in variants for w in wl for r in range(args.repeat) for t in tools]:
             if args.pause:
                 time.sleep(args.pause)
             extra = (["--devices", args.devices] if args.devices else []) + v.split()
-            wall, inner, o_ours = run(ours, r1, r2, tmp, "amd", args.config, w, extra, args.null_out)
-            line = {"tool": "fqtool-amd", "config": args.config, "pairs": args.pairs, "fastq_GB": round(gb, 3),
+            wall, inner, o_ours = run(binary, r1, r2, tmp, "amd", args.config, w, extra, args.null_out)
+            line = {"tool": name, "config": args.config, "pairs": args.pairs, "fastq_GB": round(gb, 3),
                     "wall_s": round(wall, 3), "Mreads_s": round(reads / wall / 1e6, 3),
                     "fastq_GB_s": round(gb / wall, 3), "workers": w, "devices": args.devices, "extra": v,
                     "text_mode": os.environ.get("FQ_TEXT_MODE", "1") != "0", "tool_log": inner}
