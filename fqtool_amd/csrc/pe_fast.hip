@@ -104,11 +104,9 @@ constexpr int kInsW = (512 + 1 + 1) & ~1;                 // insert-size histogr
 constexpr int kAdCW = 10;    // words of an adapter column (positions < FQ_MAX_ADAPTER, + one look-ahead)
 constexpr int kAdRc = 144;   // read 2's adapter column: index y holds position kAdRc - 1 - y
 static_assert(kAdRc >= FQ_MAX_ADAPTER + 15 && kAdRc + 16 <= 16 * kAdCW && FQ_MAX_ADAPTER + 16 <= 16 * kAdCW, "adapter column");
-// adapter bytes of both mates, adseq_search's window words [2][8], adapter columns [2][kAdCW] and the
-// (fh, fl) words of each mate's first window [2][16][2]
-constexpr int kAdWinOff = 2 * FQ_MAX_ADAPTER / 4, kAdColOff = kAdWinOff + 16, kAdBitOff = kAdColOff + 2 * kAdCW;
-constexpr int kAdW = kAdBitOff + 2 * 16 * 2;
-static_assert(kAdBitOff % 2 == 0, "(fh, fl) pairs 8-byte aligned");
+// adapter bytes of both mates, adseq_search's window words [2][8] and adapter columns [2][kAdCW]
+constexpr int kAdWinOff = 2 * FQ_MAX_ADAPTER / 4, kAdColOff = kAdWinOff + 16;
+constexpr int kAdW = kAdColOff + 2 * kAdCW;
 // per-read scalars are spread over kScalCopies LDS copies (lane % copies), each
 // [4 stats][reads, length_sum, q20, q30] u64, 17 u64 apart (not 16: the copies then sit on distinct
 // LDS bank pairs); the merge variant keeps 8 copies (LDS budget)
@@ -448,9 +446,19 @@ __device__ __forceinline__ uint32_t unzip2(uint32_t x) {
     return __builtin_amdgcn_perm(x, x, 0x03010200u);  // swap bytes 1 and 2
 }
 
-// Full-adder step of the carry-save counters: (hi, lo) = a + b + c, bitwise
+// Full-adder step of the carry-save counters: (hi, lo) = a + b + c, bitwise.  One v_bitop3 each for
+// the majority and the parity (full rate); left to itself the compiler shares a ^ b between them and
+// takes the majority by a half-rate v_bfi or a third op.
 __device__ __forceinline__ void csa(uint32_t& hi, uint32_t& lo, uint32_t a, uint32_t b, uint32_t c) {
-    const uint32_t h = (a & b) | (a & c) | (b & c), l = a ^ b ^ c;
+    uint32_t h, l;
+    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xE8" : "=v"(h) : "v"(a), "v"(b), "v"(c));  // (a & b) | (a & c) | (b & c)
+    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(l) : "v"(a), "v"(b), "v"(c));  // a ^ b ^ c
+    hi = h;
+    lo = l;
+}
+// Half-adder step: (hi, lo) = a + b
+__device__ __forceinline__ void ha(uint32_t& hi, uint32_t& lo, uint32_t a, uint32_t b) {
+    const uint32_t h = a & b, l = a ^ b;
     hi = h;
     lo = l;
 }
@@ -462,32 +470,10 @@ __device__ __forceinline__ void csa(uint32_t& hi, uint32_t& lo, uint32_t a, uint
 // bit planes H and L over positions; for compared position j the mismatch vector over the 32
 // offsets of a block is ((H >> j) ^ FH_j) | ((L >> j) ^ FL_j) (FH_j, FL_j = the bits of fixed[j]
 // spread over a word), and the 16 vectors are summed per offset with carry-save adders.
-// Compared position j's fixed code bits, each as a word of 0s or 1s (fh: high bit, fl: low bit):
-//  * FixedOwn: from the lane's own fixed word (the overlap: a window of the other mate), two v_bfe;
-//  * FixedLds: precomputed in LDS (trimBySequence: the adapter's first 16 codes, the same for every
-//    lane of a mate), one broadcast ds_read_b64 and no VALU.  Measured slower than FixedOwn there and
-//    not instantiated at present; its LDS words are still filled at kernel start (pe_fast_kernel).
-struct FixedOwn {
-    uint32_t fu;  // unzip2(fixed)
-    __device__ __forceinline__ void next_block() {}
-    __device__ __forceinline__ void bits(int j, uint32_t& fh, uint32_t& fl) const {
-        fh = (uint32_t)__builtin_amdgcn_sbfe((int)fu, 16 + j, 1);
-        fl = (uint32_t)__builtin_amdgcn_sbfe((int)fu, j, 1);
-    }
-};
-struct FixedLds {
-    uint32_t f;  // LDS byte address of [j] = (fh, fl)
-    // (opaque per block: hoisted out of the block loop, the 32 words would stay live and spill)
-    __device__ __forceinline__ void next_block() { asm volatile("" : "+v"(f)); }
-    __device__ __forceinline__ void bits(int j, uint32_t& fh, uint32_t& fl) const {
-        typedef __attribute__((address_space(3))) const uint32_t LdsW;
-        const LdsW* w = reinterpret_cast<const LdsW*>((size_t)f);
-        fh = w[2 * j];
-        fl = w[2 * j + 1];
-    }
-};
-template <class FX>
-__device__ inline void ov_candidates(const uint32_t* col, int cm, int mpos, FX fx, int K, int cnt,
+// FH_j and FL_j come from fu = unzip2(fixed) by one v_bfe_i32 each; they depend on j only, and the
+// compiler takes all 32 once, ahead of the block loop, and keeps them in registers (no spill in any
+// instantiation: check with tools/resusage.py after a change here).
+__device__ inline void ov_candidates(const uint32_t* col, int cm, int mpos, uint32_t fu, int K, int cnt,
                                      uint32_t cand[kOvBlocks]) {
     // planes of the 32 positions from mpos + 32 * i (i = block): low-bit plane, high-bit plane,
     // from a stream of the column's code words (two new LDS words per block).  Unclamped: mpos >= 0,
@@ -519,7 +505,6 @@ __device__ inline void ov_candidates(const uint32_t* col, int cm, int mpos, FX f
     for (int i = 0; i < kOvBlocks; ++i) creg[i] = 0u;
 #pragma unroll 1
     for (int bk = 0; bk < nblk; ++bk) {
-        fx.next_block();
         if (bk < kOvBlocks - 1) planes(L1, H1);
         else L1 = H1 = 0u;
         // mismatch vector of compared position j over the block's 32 offsets
@@ -532,20 +517,21 @@ __device__ inline void ov_candidates(const uint32_t* col, int cm, int mpos, FX f
         auto m = [&](int j) -> uint32_t {
             const uint32_t hs = j ? shr64(HA, j) : H0;
             const uint32_t ls = j ? shr64(LA, j) : L0;
-            uint32_t fh, fl;
-            fx.bits(j, fh, fl);
+            const uint32_t fh = (uint32_t)__builtin_amdgcn_sbfe((int)fu, 16 + j, 1);
+            const uint32_t fl = (uint32_t)__builtin_amdgcn_sbfe((int)fu, j, 1);
             return (hs ^ fh) | (ls ^ fl);
         };
         uint32_t lt;
-        // 16 vectors -> bit-sliced 5-bit counts, Harley-Seal carry-save order (few live values)
-        uint32_t ones = 0u, twos = 0u, fours = 0u, eights = 0u, sixteen, twosA, twosB, foursA, foursB, eightsA, eightsB;
-        csa(twosA, ones, ones, m(0), m(1));
+        // 16 vectors -> bit-sliced 5-bit counts, Harley-Seal carry-save order (few live values); the
+        // first step of each level adds into an empty counter
+        uint32_t ones, twos, fours, eights, sixteen, twosA, twosB, foursA, foursB, eightsA, eightsB;
+        ha(twosA, ones, m(0), m(1));
         csa(twosB, ones, ones, m(2), m(3));
-        csa(foursA, twos, twos, twosA, twosB);
+        ha(foursA, twos, twosA, twosB);
         csa(twosA, ones, ones, m(4), m(5));
         csa(twosB, ones, ones, m(6), m(7));
         csa(foursB, twos, twos, twosA, twosB);
-        csa(eightsA, fours, fours, foursA, foursB);
+        ha(eightsA, fours, foursA, foursB);
         csa(twosA, ones, ones, m(8), m(9));
         csa(twosB, ones, ones, m(10), m(11));
         csa(foursA, twos, twos, twosA, twosB);
@@ -554,9 +540,9 @@ __device__ inline void ov_candidates(const uint32_t* col, int cm, int mpos, FX f
         csa(foursB, twos, twos, twosA, twosB);
         csa(eightsB, fours, fours, foursA, foursB);
         if (K == 5) {  // the default overlap_diff_limit: count < 5 <=> no 8s or 16s, not (4 and (2 or 1))
-            lt = ~(eights | eightsA | eightsB | (fours & (twos | ones)));
+            lt = ~(eightsA | eightsB | (fours & (twos | ones)));
         } else {  // count < K, bit-sliced against the wave-uniform K
-            csa(sixteen, eights, eights, eightsA, eightsB);
+            ha(sixteen, eights, eightsA, eightsB);
             uint32_t eq = ~0u;
             lt = 0u;
             const uint32_t cb[5] = {ones, twos, fours, eights, sixteen};
@@ -601,11 +587,9 @@ __device__ inline void ov_candidates(const uint32_t* col, int cm, int mpos, FX f
 // shares its code with some upper-case letter), so it never exceeds the byte count: a pos it
 // rejects has more mismatches than allowed.  Valid for adapters of >= 20 upper-case ACGT bytes
 // (start = -4, and the windows of every negative pos lie inside the adapter's first 20 positions);
-// the kernel start sets adw[5], the window words, the adapter column and its bit words (see
-// pe_fast_kernel).
+// the kernel start sets adw[5], the window words and the adapter column (see pe_fast_kernel).
 //  * pos in [0, n - 16]: full 16-position windows, all at once (ov_candidates; bound < alen/8 + 1,
-//    a superset of every pos's own allowance), the adapter's bits per compared position by two v_bfe
-//    from the window word (FixedOwn; adf, the LDS address of FixedLds's words, is not used);
+//    a superset of every pos's own allowance), against the adapter's first window word;
 //  * pos in -4..-1 and [n - 15, n - 5]: one masked window each against that pos's allowance.
 // The survivors' test is the reference's byte comparison restated on the columns, 16 positions a
 // step: with an upper-case ACGT adapter a read byte differs from the adapter byte iff its code
@@ -616,7 +600,7 @@ __device__ inline void ov_candidates(const uint32_t* col, int cm, int mpos, FX f
 // kMaxLen - 1 - st - j), so its windows run down the column and its adapter words are stored
 // reversed and complemented; `fixed` word k = codes of adapter positions k .. k + 15.
 __device__ inline bool adseq_search(const uint32_t* col, int c, bool rc, int st, int n, const uint32_t* adw,
-                                    const uint32_t* adc, uint32_t adf, int alen, int& pos_out) {
+                                    const uint32_t* adc, int alen, int& pos_out) {
     // The reference's inner loop at pos (src/adaptertrimmer.cpp:59-71) on the columns, 16 positions a
     // step: with an upper-case ACGT adapter a read byte differs from the adapter's iff its code
     // differs or it is not an upper-case A C G T (an N, a lowercase or an exotic byte: the N word's
@@ -654,7 +638,7 @@ __device__ inline bool adseq_search(const uint32_t* col, int c, bool rc, int st,
     }
     if (n >= 16) {
         uint32_t cand[kOvBlocks];
-        ov_candidates(col, c, rc ? kMaxLen - st - n : st, FixedOwn{unzip2(adw[0])}, alen / 8 + 1, n - 15, cand);
+        ov_candidates(col, c, rc ? kMaxLen - st - n : st, unzip2(adw[0]), alen / 8 + 1, n - 15, cand);
         for (;;) {  // candidates in pos order: read 1 from the lowest offset, read 2 from the highest
             int k = -1;
             if (!rc) {
@@ -1173,17 +1157,6 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
             if (q >= 0 && q < FQ_MAX_ADAPTER) v |= (uint32_t)(((a[q] >> 1) & 3) ^ (m ? 2 : 0)) << (2 * f);
         }
         adw[kAdColOff - kAdWinOff + m * kAdCW + w] = v;
-    } else if (threadIdx.x >= 64 && threadIdx.x < 64 + 2 * 16) {
-        // (fh, fl) of compared position j of each mate's first window (adw[8 m], as ov_candidates'
-        // FixedOwn would derive them), for FixedLds
-        const int m = (threadIdx.x - 64) >> 4, j = (threadIdx.x - 64) & 15;
-        const uint8_t* a = m ? p.adapter2 : p.adapter1;
-        uint32_t w = 0;
-        for (int f = 0; f < 16; ++f) w |= (uint32_t)((a[f] >> 1) & 3) << (2 * f);
-        if (m) w = pairrev(w) ^ 0xAAAAAAAAu;
-        const uint32_t fu = unzip2(w);
-        adw[kAdBitOff - kAdWinOff + 2 * (16 * m + j)] = 0u - ((fu >> (16 + j)) & 1u);
-        adw[kAdBitOff - kAdWinOff + 2 * (16 * m + j) + 1] = 0u - ((fu >> j) & 1u);
     }
     __syncthreads();
 
@@ -1532,9 +1505,7 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
         auto by_sequence = [&]() {
             int pos;
             const uint32_t* my_adw = adw + 8 * mate;
-            if (my_adw[5] ? adseq_search(col, lane, rc, st, n, my_adw, adw + (kAdColOff - kAdWinOff) + kAdCW * mate,
-                                         (uint32_t)(size_t)(const __attribute__((address_space(3))) uint32_t*)(adw + (kAdBitOff - kAdWinOff) + 32 * mate),
-                                         my_alen, pos)
+            if (my_adw[5] ? adseq_search(col, lane, rc, st, n, my_adw, adw + (kAdColOff - kAdWinOff) + kAdCW * mate, my_alen, pos)
                           : trim_by_sequence_t(at(seq, st), n, my_ad, my_alen, pos)) {
                 int ad_len;
                 if (pos < 0) {
@@ -1573,7 +1544,7 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
             const bool planes = req >= 16 && !__any(olB < 16) && !(abl & 128);
             if (planes) {
                 uint32_t cand[kOvBlocks];
-                ov_candidates(col, cm, mpos, FixedOwn{unzip2(fixed)}, K, cnt, cand);
+                ov_candidates(col, cm, mpos, unzip2(fixed), K, cnt, cand);
                 for (;;) {  // candidates in offset order until one passes the exact test
                     int o = -1;
 #pragma unroll

@@ -4,7 +4,7 @@ import re, subprocess, sys
 cur = None
 rows = []
 for line in sys.stdin:
-    m = re.search(r"remark:\s+(Function Name|TotalSGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\]):\s*(\S+)", line)
+    m = re.search(r"remark:\s+(?:\S+:\d+:\d+:\s+)?(Function Name|TotalSGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\]):\s*(\S+)", line)
     if not m:
         continue
     k, v = m.groups()
