@@ -118,6 +118,11 @@ class FqEgress(ctypes.Structure):  # fq_egress
     _fields_ = [("open", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class FqUmi(ctypes.Structure):  # fq_umi
+    _fields_ = [("location", ctypes.c_int32), ("length", ctypes.c_int32), ("skip", ctypes.c_int32),
+                ("drop_comment", ctypes.c_uint8), ("not_trim", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 2)]
+
+
 class FqEgressOut(ctypes.Structure):  # fq_egress_out
     _fields_ = [("text", ctypes.c_void_p * FQ_EG_STREAMS), ("cap", ctypes.c_uint64 * FQ_EG_STREAMS),
                 ("bytes", ctypes.c_uint64 * FQ_EG_STREAMS)]
@@ -325,6 +330,9 @@ def load_engine(path=ENGINE_LIB):
     lib.fq_engine_set_egress.argtypes = [vp, ctypes.POINTER(FqEgress)]
     lib.fq_engine_submit_text_routed.argtypes = [vp, ctypes.POINTER(FqTextBatch), vp, ctypes.POINTER(FqEgressOut), u64]
     lib.fq_engine_raw_launch_routed.argtypes = [vp, ctypes.POINTER(FqRawResult), ctypes.POINTER(FqRawEgressOut), u64]
+    lib.fq_engine_set_umi.argtypes = [vp, ctypes.POINTER(FqUmi)]
+    lib.fq_egress_bound_umi.argtypes = [i32, u64, u64, u64, ctypes.POINTER(FqUmi)]
+    lib.fq_egress_bound_umi.restype = ctypes.c_size_t
     cs = ctypes.c_size_t
     lib.fq_inflate_create.argtypes = [ctypes.c_int, cs, cs, cs, ctypes.POINTER(vp)]
     lib.fq_inflate_destroy.argtypes = [vp]
@@ -345,6 +353,7 @@ ENGINE_SYMBOLS = [
     "fq_engine_raw_begin", "fq_engine_raw_enqueue", "fq_engine_raw_launch", "fq_engine_raw_wait", "fq_engine_raw_end", "fq_host_register", "fq_host_unregister",
     "fq_deflate_bound", "fq_deflate_code_lengths", "fq_deflate_create", "fq_deflate_destroy", "fq_deflate_bgzf",
     "fq_engine_set_gz_out", "fq_egress_bound", "fq_engine_set_egress", "fq_engine_submit_text_routed", "fq_engine_raw_launch_routed",
+    "fq_engine_set_umi", "fq_egress_bound_umi",
     "fq_inflate_create", "fq_inflate_destroy", "fq_inflate_members", "fq_inflate_bgzf", "fq_inflate_last_kernel_ms",
     "fq_kstat_create", "fq_kstat_destroy", "fq_kstat_reset", "fq_kstat_k", "fq_kstat_words", "fq_engine_set_kstat",
     "fq_kstat_read", "fq_kstat_last_kernel_ms",

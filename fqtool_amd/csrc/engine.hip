@@ -131,6 +131,9 @@ struct fq_engine {
     // routed egress (fq_engine_set_egress): the streams that have a writer
     bool eg_on = false;
     uint32_t eg_open = 0;
+    // UMI description of the routed egress (fq_engine_set_umi)
+    bool umi_on = false;
+    fq_umi umi{};
     uint64_t calls = 0;       // order of process / process_device packs for the table
     std::string last_error;
 };
@@ -699,7 +702,7 @@ int fq_engine_submit_text(fq_engine* e, const fq_text_batch* tb, fq_read_result*
     const bool pe = e->p.paired;
     if (tb->n < 0 || tb->n > e->max_batch || tb->stride <= 0 || tb->stride > e->max_stride || (tb->stride & 15))
         return fail(e, FQ_E_INVALID, "text pack exceeds the engine's max_batch/max_stride (or stride % 16 != 0)");
-    if (e->p.correction_enabled || e->p.umi_front1 > 0 || e->p.umi_front2 > 0 ||
+    if (e->p.correction_enabled || e->p.umi_front1 > 0 || e->p.umi_front2 > 0 || e->umi_on ||
         (e->p.merge_enabled && e->p.discard_unmerged))
         return fail(e, FQ_E_INVALID, "text packs take no -c, UMI or --discard_unmerged options");
     for (int m = 0; m < (pe ? 2 : 1); ++m)
@@ -806,6 +809,55 @@ size_t fq_egress_bound(int32_t stream, uint64_t text_bytes1, uint64_t text_bytes
     }
 }
 
+// what the UMI tag can add to stream s (include/fqengine.h)
+size_t fq_egress_bound_umi(int32_t stream, uint64_t text_bytes1, uint64_t text_bytes2, uint64_t n, const fq_umi* u) {
+    const size_t base = fq_egress_bound(stream, text_bytes1, text_bytes2, n);
+    if (!u || !base) return base;
+    const bool pe = text_bytes2 != 0;
+    const size_t L = (size_t)std::max<int32_t>(u->length, 0);
+    // records of the stream, and how often one mate's name can recur in its tags
+    const size_t recs = (size_t)n * ((stream == FQ_EG_MERGED || stream == FQ_EG_FAILED) && pe ? 2 : 1);
+    const size_t per = recs / (n ? (size_t)n : 1);
+    switch (u->location) {
+        case 3: case 4: return base + recs * (12 + 2 * L);
+        case 6: return base + recs * (14 + 4 * L);
+        case 1: return base + recs * 6 + per * (size_t)text_bytes1;
+        case 2: return base + recs * 6 + per * (size_t)text_bytes2;
+        default: return base + recs * 7 + per * ((size_t)text_bytes1 + (size_t)text_bytes2);
+    }
+}
+
+// the description against the engine's params (Options::umi_front)
+static bool umi_matches(const fq_params& p, const fq_umi& u) {
+    const int front = u.not_trim ? 0 : u.length + u.skip;
+    const bool r1 = u.location == 3 || u.location == 6, r2 = (u.location == 4 || u.location == 6) && p.paired;
+    return p.umi_front1 == (r1 ? front : 0) && p.umi_front2 == (r2 ? front : 0);
+}
+
+int fq_engine_set_umi(fq_engine* e, const fq_umi* u) {
+    if (!e) return FQ_E_INVALID;
+    if (!e->pending.empty() || !e->raw_queued.empty()) return fail(e, FQ_E_INVALID, "fq_engine_set_umi with packs in flight");
+    if (e->raw) return fail(e, FQ_E_INVALID, "fq_engine_set_umi inside a raw stream");
+    if (u) {
+        if (u->location < 1 || u->location > 6 || u->length < 0 || u->skip < 0 || u->length > 65535 || u->skip > 65535)
+            return fail(e, FQ_E_INVALID, "fq_engine_set_umi: location must be 1..6, length and skip 0..65535");
+        if ((u->location == 3 || u->location == 4 || u->location == 6) && u->length == 0)
+            return fail(e, FQ_E_INVALID, "fq_engine_set_umi: the UMI length can not be zero in read 1 / 2");
+        if (u->drop_comment > 1 || u->not_trim > 1 || u->reserved[0] || u->reserved[1])
+            return fail(e, FQ_E_INVALID, "fq_engine_set_umi: flags must be 0 or 1, reserved 0");
+        if (!umi_matches(e->p, *u))
+            return fail(e, FQ_E_INVALID, "fq_engine_set_umi: the description disagrees with the params' umi_front1/2");
+    }
+    for (Slot& s : e->slots) s.raw_ready = false;  // (raw slots carry the open streams' buffers at their bounds)
+    e->umi_on = u != nullptr;
+    e->umi = u ? *u : fq_umi{};
+    return FQ_OK;
+}
+
+// the routed calls take UMI params only with a description set (which set_umi checked against them)
+static bool umi_refused(const fq_engine* e) { return !e->umi_on && (e->p.umi_front1 > 0 || e->p.umi_front2 > 0); }
+static const fq_umi* umi_of(const fq_engine* e) { return e->umi_on ? &e->umi : nullptr; }
+
 int fq_engine_set_egress(fq_engine* e, const fq_egress* eg) {
     if (!e) return FQ_E_INVALID;
     if (!e->pending.empty() || !e->raw_queued.empty()) return fail(e, FQ_E_INVALID, "fq_engine_set_egress with packs in flight");
@@ -838,7 +890,7 @@ static int ensure_egress_caps(fq_engine* e, Slot& s, uint64_t text1, uint64_t te
             HIP_TRY(e, hipMalloc(&s.d_egoff[k], recs * sizeof(uint32_t)));
             s.eg_recs[k] = recs;
         }
-        const size_t need = fq_egress_bound(k, text1, text2, (uint64_t)n);
+        const size_t need = fq_egress_bound_umi(k, text1, text2, (uint64_t)n, umi_of(e));
         if (need > s.eg_cap[k]) {
             if (s.d_eg[k]) (void)hipFree(s.d_eg[k]);
             s.d_eg[k] = nullptr;
@@ -861,7 +913,7 @@ int fq_engine_submit_text_routed(fq_engine* e, const fq_text_batch* tb, fq_read_
     if (e->raw) return fail(e, FQ_E_INVALID, "routed text pack inside a raw stream");
     if (tb->n < 0 || tb->n > e->max_batch || tb->stride <= 0 || tb->stride > e->max_stride || (tb->stride & 15))
         return fail(e, FQ_E_INVALID, "text pack exceeds the engine's max_batch/max_stride (or stride % 16 != 0)");
-    if (e->p.umi_front1 > 0 || e->p.umi_front2 > 0) return fail(e, FQ_E_INVALID, "routed text packs take no UMI options");
+    if (umi_refused(e)) return fail(e, FQ_E_INVALID, "routed text packs take no UMI options");
     if (e->p.correction_enabled && tb->stride > 32768)
         return fail(e, FQ_E_INVALID, "-c takes reads of at most 32767 bases (the record's overlap offset is 16-bit)");
     for (int m = 0; m < mates; ++m)
@@ -870,7 +922,8 @@ int fq_engine_submit_text_routed(fq_engine* e, const fq_text_batch* tb, fq_read_
     for (int k = 0; k < FQ_EG_STREAMS; ++k) {
         out->bytes[k] = 0;
         if (!((e->eg_open >> k) & 1u)) continue;
-        const size_t need = fq_egress_bound(k, tb->text_bytes[0], pe ? tb->text_bytes[1] : 0, (uint64_t)tb->n);
+        const size_t need = fq_egress_bound_umi(k, tb->text_bytes[0], pe ? tb->text_bytes[1] : 0, (uint64_t)tb->n, umi_of(e));
+        if (e->umi_on && need > 0xFFFFFFFFull) return fail(e, FQ_E_INVALID, "routed text pack: a UMI-tagged stream's bound exceeds the 32-bit cursors (submit smaller packs)");
         if (!out->text[k] || out->cap[k] < need)
             return fail(e, FQ_E_INVALID, "routed text pack: an open stream's buffer is missing or below fq_egress_bound");
     }
@@ -928,6 +981,7 @@ int fq_engine_submit_text_routed(fq_engine* e, const fq_text_batch* tb, fq_read_
     a.n = tb->n, a.stride = tb->stride, a.paired = pe ? 1 : 0;
     a.merge = pe && e->p.merge_enabled, a.discard = e->p.discard_unmerged;
     a.open = e->eg_open;
+    a.umi = umi_of(e);
     for (int q = 0; q < FQ_EG_STREAMS; ++q) st.size[q] = s.d_egsize[q], st.off[q] = s.d_egoff[q], st.out[q] = s.d_eg[q];
     st.total = s.d_egtotal;
     HIP_TRY(e, fq_launch_egress(a, st, s.d_scan, s.scan_bytes, e->stream));
@@ -1012,7 +1066,8 @@ int fq_engine_raw_begin(fq_engine* e, uint64_t window_cap, uint64_t carry_cap) {
     if (!e) return FQ_E_INVALID;
     if (!e->pending.empty() || !e->raw_queued.empty()) return fail(e, FQ_E_INVALID, "fq_engine_raw_begin with packs in flight");
     // (-c and --discard_unmerged: only with an egress set, whose packs fq_engine_raw_launch_routed writes)
-    if (e->p.umi_front1 > 0 || e->p.umi_front2 > 0 ||
+    // (UMI: with an egress and a UMI description set)
+    if ((e->umi_on && !e->eg_on) || (!(e->umi_on && e->eg_on) && (e->p.umi_front1 > 0 || e->p.umi_front2 > 0)) ||
         (!e->eg_on && (e->p.correction_enabled || (e->p.merge_enabled && e->p.discard_unmerged))))
         return fail(e, FQ_E_INVALID, "raw streams take no -c, UMI or --discard_unmerged options");
     if (e->p.correction_enabled && e->max_stride > 32768)
@@ -1129,7 +1184,7 @@ int fq_engine_raw_launch(fq_engine* e, fq_raw_result* r, fq_raw_out* out, uint64
     if (e->raw_queued.empty()) return fail(e, FQ_E_INVALID, "fq_engine_raw_launch without an enqueued window");
     if (e->gz_level && out->results) return fail(e, FQ_E_INVALID, "raw pack: records-only egress while gz output is on");
     // (its two streams cannot hold what -c and --discard_unmerged write: fq_engine_raw_launch_routed)
-    if (e->p.correction_enabled || (e->p.merge_enabled && e->p.discard_unmerged))
+    if (e->p.correction_enabled || (e->p.merge_enabled && e->p.discard_unmerged) || e->umi_on)
         return fail(e, FQ_E_INVALID, "raw streams take no -c, UMI or --discard_unmerged options");
     HIP_TRY(e, hipSetDevice(e->device));
     const int k = e->raw_queued.front();
@@ -1238,7 +1293,8 @@ int fq_engine_raw_launch_routed(fq_engine* e, fq_raw_result* r, fq_raw_egress_ou
     for (int q = 0; q < FQ_EG_STREAMS; ++q) {
         out->eg.bytes[q] = 0;
         if (!((e->eg_open >> q) & 1u) || n <= 0) continue;
-        const size_t need = fq_egress_bound(q, r->text_bytes[0], pe ? r->text_bytes[1] : 0, (uint64_t)n);
+        const size_t need = fq_egress_bound_umi(q, r->text_bytes[0], pe ? r->text_bytes[1] : 0, (uint64_t)n, umi_of(e));
+        if (e->umi_on && need > 0xFFFFFFFFull) return fail(e, FQ_E_INVALID, "routed raw pack: a UMI-tagged stream's bound exceeds the 32-bit cursors (use smaller windows and max_batch)");
         if (!out->eg.text[q] || out->eg.cap[q] < need)
             return fail(e, FQ_E_INVALID, "routed raw pack: an open stream's buffer is missing or below fq_egress_bound");
     }
@@ -1285,6 +1341,7 @@ int fq_engine_raw_launch_routed(fq_engine* e, fq_raw_result* r, fq_raw_egress_ou
     a.n = n, a.stride = db.stride, a.paired = pe ? 1 : 0;
     a.merge = pe && e->p.merge_enabled, a.discard = e->p.discard_unmerged;
     a.open = e->eg_open;
+    a.umi = umi_of(e);
     for (int q = 0; q < FQ_EG_STREAMS; ++q) st.size[q] = s.d_egsize[q], st.off[q] = s.d_egoff[q], st.out[q] = s.d_eg[q];
     st.total = s.d_egtotal;
     HIP_TRY(e, fq_launch_egress(a, st, s.d_scan, s.scan_bytes, e->stream));

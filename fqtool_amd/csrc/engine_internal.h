@@ -70,6 +70,7 @@ struct fq_egress_args {
     const uint8_t* qual[2];
     int n, stride, paired, merge, discard;
     uint32_t open;
+    const fq_umi* umi;       // the UMI description (fq_engine_set_umi), or null
 };
 struct fq_egress_streams {
     uint32_t* size[FQ_EG_STREAMS];  // n each, open streams only

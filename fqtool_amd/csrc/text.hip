@@ -220,14 +220,19 @@ __global__ void merge_write_kernel(const char* __restrict__ text1, const char* _
 // ---- routed egress (fq_engine_set_egress): six streams, the per-pair routine of egress_core.h ----
 // One lane per pair: egress_size_kernel stores the bytes the pair adds to each open stream, one
 // exclusive scan per open stream turns them into the pair's cursors, egress_write_kernel writes.
+// UMI (fq_engine_set_umi): the instantiation of a pack with a UMI description builds the pair's tag
+// (four slices of the input text, kept in registers) and writes the tagged names; the other one is
+// the code as it was.  Both passes derive the tag the same way, so sizes and bytes agree.
+template <bool UMI>
 __global__ void egress_size_kernel(fqegress::Pack pk, fq_egress_streams st) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= pk.n) return;
     fqegress::Mate m[2];
     bool planes;
-    const fqegress::Plan p = fqegress::load(pk, i, m, planes);
+    const fqegress::Plan p = fqegress::load<UMI>(pk, i, m, planes);
     uint32_t z[FQ_EG_STREAMS];
-    fqegress::sizes(p, m, z);
+    if (UMI) fqegress::sizes(p, m, z, p.n ? fqegress::umi_tag(pk.umi, pk.paired != 0, m) : fqegress::Tag{}, pk.umi.drop_comment != 0);
+    else fqegress::sizes(p, m, z);
 #pragma unroll
     for (int s = 0; s < FQ_EG_STREAMS; ++s)
         if ((pk.open >> s) & 1u) st.size[s][i] = z[s];
@@ -239,17 +244,19 @@ __global__ void egress_total_kernel(fq_egress_streams st, uint32_t open, int n) 
     st.total[s] = ((open >> s) & 1u) && n ? (unsigned long long)st.off[s][n - 1] + st.size[s][n - 1] : 0ull;
 }
 
+template <bool UMI>
 __global__ void egress_write_kernel(fqegress::Pack pk, fq_egress_streams st) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= pk.n) return;
     fqegress::Mate m[2];
     bool planes;
-    const fqegress::Plan p = fqegress::load(pk, i, m, planes);
+    const fqegress::Plan p = fqegress::load<UMI>(pk, i, m, planes);
     if (!p.n) return;
     char* d[FQ_EG_STREAMS];
 #pragma unroll
     for (int s = 0; s < FQ_EG_STREAMS; ++s) d[s] = ((pk.open >> s) & 1u) ? st.out[s] + st.off[s][i] : nullptr;
-    fqegress::write(p, m, planes, d);
+    if (UMI) fqegress::write(p, m, planes, d, fqegress::umi_tag(pk.umi, pk.paired != 0, m), pk.umi.drop_comment != 0);
+    else fqegress::write(p, m, planes, d);
 }
 
 // trimmed-adapter entries of a routed raw pack (raw.hip's entry format, from the buffer's start): the
@@ -272,7 +279,8 @@ __global__ void egress_ad_write_kernel(fqegress::Pack pk, int m, const uint32_t*
     fqegress::Mate mt[2];
     bool planes;
     fqegress::load(pk, i, mt, planes);
-    const fqegress::Mate& M = mt[pk.paired ? m : 0];
+    fqegress::Mate M = mt[0];  // (a copy: indexing mt with a run-time value would put it in scratch memory)
+    if (pk.paired && m) M = mt[1];
     const fq_read_result& r = M.r;
     char* d = out + off[i];
     d[0] = (char)(r.ad_len & 0xFF);
@@ -292,6 +300,7 @@ static fqegress::Pack egress_pack(const fq_egress_args& a) {
     for (int m = 0; m < 2; ++m) pk.text[m] = a.text[m], pk.rec[m] = a.rec[m], pk.seq[m] = a.seq[m], pk.qual[m] = a.qual[m];
     pk.res = a.res;
     pk.n = a.n, pk.stride = a.stride, pk.paired = a.paired, pk.merge = a.merge, pk.discard = a.discard, pk.open = a.open;
+    if (a.umi) pk.umi = fqegress::Umi{a.umi->location, a.umi->length, a.umi->skip, a.umi->drop_comment, a.umi->not_trim};
     return pk;
 }
 
@@ -318,7 +327,8 @@ hipError_t fq_launch_egress(const fq_egress_args& a, const fq_egress_streams& st
     if (a.n <= 0) return hipMemsetAsync(st.total, 0, FQ_EG_STREAMS * sizeof(unsigned long long), s);
     const fqegress::Pack pk = egress_pack(a);
     const dim3 g((a.n + 255) / 256), b(256);
-    hipLaunchKernelGGL(egress_size_kernel, g, b, 0, s, pk, st);
+    if (pk.umi.location) hipLaunchKernelGGL(egress_size_kernel<true>, g, b, 0, s, pk, st);
+    else hipLaunchKernelGGL(egress_size_kernel<false>, g, b, 0, s, pk, st);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     for (int k = 0; k < FQ_EG_STREAMS; ++k) {
@@ -328,7 +338,8 @@ hipError_t fq_launch_egress(const fq_egress_args& a, const fq_egress_streams& st
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(egress_total_kernel, dim3(1), dim3(64), 0, s, st, a.open, a.n);
-    hipLaunchKernelGGL(egress_write_kernel, g, b, 0, s, pk, st);
+    if (pk.umi.location) hipLaunchKernelGGL(egress_write_kernel<true>, g, b, 0, s, pk, st);
+    else hipLaunchKernelGGL(egress_write_kernel<false>, g, b, 0, s, pk, st);
     return hipGetLastError();
 }
 

@@ -37,6 +37,9 @@
 #pragma weak fq_egress_bound
 #pragma weak fq_engine_submit_text_routed
 #pragma weak fq_engine_raw_launch_routed
+// UMI (-u) on the routed egress: without these calls UMI runs keep the host packs
+#pragma weak fq_engine_set_umi
+#pragma weak fq_egress_bound_umi
 // The k-mer statistics (--kmer --kmer_length) are bound weakly too; without them such a run fails
 // with a message instead of leaving the KmerCount sections out.
 #pragma weak fq_kstat_create
@@ -1435,6 +1438,16 @@ struct Lane {
     int gz_level = 0;       // FQ_GZ_DEVICE=1 with .gz outputs: text / raw packs come back as BGZF members
     bool routed = false;    // routed egress: text packs come back as the Sink's writers' streams
     uint32_t eg_open = 0;   // ... those writers, as FQ_EG_* bits
+    bool umi_on = false;    // -u on the routed egress: the engine tags the names (fq_engine_set_umi)
+    fq_umi umi{};
+    // a routed stream's buffer capacity for a pack.  (The engine refuses a UMI-tagged stream whose bound
+    // passes 2^32 - 1, its cursors being 32-bit; this is not checked here before a window is sized: at
+    // the index locations FAILED's bound is up to three times both mates' text, so windows of 48 MiB
+    // and packs of 128 Ki pairs stay below it by a factor of ten.  Larger --pack_pairs would meet the
+    // engine's refusal, which says what to do.)
+    size_t eg_bound(int s, uint64_t t1, uint64_t t2, uint64_t n) const {
+        return umi_on ? fq_egress_bound_umi(s, t1, t2, n, &umi) : fq_egress_bound(s, t1, t2, n);
+    }
     // an output buffer of x bytes of text, sized for its members instead
     size_t out_cap(size_t x) const { return gz_level ? fq_deflate_bound(x) : x; }
     int max_cycles = 0, max_batch = 0, max_stride = 0;
@@ -1473,6 +1486,8 @@ struct Lane {
             const fq_egress eg{eg_open, 0};
             if (fq_engine_set_egress(e, &eg) != FQ_OK)
                 throw std::runtime_error(std::string("fq_engine_set_egress: ") + fq_engine_last_error(e));
+            if (umi_on && fq_engine_set_umi(e, &umi) != FQ_OK)
+                throw std::runtime_error(std::string("fq_engine_set_umi: ") + fq_engine_last_error(e));
         }
         max_cycles = cycles;
         max_batch = batch;
@@ -1526,7 +1541,7 @@ struct Lane {
                 pk.eout = fq_egress_out{};
                 for (int s = 0; s < FQ_EG_STREAMS; ++s) {
                     if (!((eg_open >> s) & 1u)) continue;
-                    const size_t cap = fq_egress_bound(s, pk.span_bytes[0], pk.paired ? pk.span_bytes[1] : 0, (uint64_t)pk.n);
+                    const size_t cap = eg_bound(s, pk.span_bytes[0], pk.paired ? pk.span_bytes[1] : 0, (uint64_t)pk.n);
                     pk.eg_text[s].resize_uninit(cap);
                     pk.eout.text[s] = pk.eg_text[s].data();
                     pk.eout.cap[s] = cap;
@@ -1881,7 +1896,7 @@ struct Lane {
                         const uint64_t t1 = cin[0] + w.n[0], t2 = mates == 2 ? cin[1] + w.n[1] : 0;
                         for (int s = 0; s < FQ_EG_STREAMS; ++s) {
                             if (!((eg_open >> s) & 1u)) continue;
-                            const size_t cap = fq_egress_bound(s, t1, t2, (uint64_t)target);
+                            const size_t cap = eg_bound(s, t1, t2, (uint64_t)target);
                             pk->eg_text[s].reserve(cap + cap / 8);
                             pk->eg_text[s].resize_uninit(cap);
                             pk->reout.eg.text[s] = pk->eg_text[s].data();
@@ -2441,13 +2456,19 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
         // another file) and -m --discard_unmerged with out1 / out2 as well.  The combinations the
         // golden fixtures do not pin keep the host packs: --unpaired_read2 alone or naming read 1's
         // file, and -m together with the failed / unpaired outputs.
+        // -u makes a run routed as well (the engine tags the names: fq_engine_set_umi), over whatever
+        // of these outputs it has, or over out1 / out2 or the merged output alone
+        // (-u without --umi_location is location 0: no tag and no cut, src/umiprocessor.cpp:10-79 -- the
+        // run goes as the run without -u that it is)
+        const bool umi_tags = o.umi && o.umi_location != 0;
+        const bool umi_ok = fq_engine_set_umi && fq_egress_bound_umi;
         const bool eg_wanted = o.correction || !o.failed_out.empty() || !o.unpaired1.empty() || !o.unpaired2.empty() ||
-                               (o.merge && o.discard_unmerged);
+                               (o.merge && o.discard_unmerged) || umi_tags;
         const bool eg_side = !o.failed_out.empty() || !o.unpaired1.empty() || !o.unpaired2.empty();
         const bool eg_unpaired_ok = o.unpaired2.empty() || (!o.unpaired1.empty() && o.unpaired1 != o.unpaired2);
         const bool eg_ok = fq_engine_set_egress && fq_egress_bound && fq_engine_submit_text_routed && eg_unpaired_ok &&
                            !(o.merge && eg_side) && (!(o.merge && o.discard_unmerged) || (!o.out1.empty() && !o.out2.empty()));
-        const bool text_mode = !(tm_env && std::string(tm_env) == "0") && (!eg_wanted || eg_ok) && !o.umi &&
+        const bool text_mode = !(tm_env && std::string(tm_env) == "0") && (!eg_wanted || eg_ok) && (!umi_tags || umi_ok) &&
                                !o.index_filter && !o.split() && !o.phred64 &&
                                (o.merge ? paired && !o.merge_out.empty()
                                         : !o.out1.empty() && (!paired || !o.out2.empty()));
@@ -2497,6 +2518,11 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
             lanes.back()->merge = o.merge && paired;
             lanes.back()->routed = routed;
             lanes.back()->eg_open = routed ? outs.egress_mask() : 0u;
+            if (routed && umi_tags) {
+                lanes.back()->umi_on = true;
+                lanes.back()->umi = fq_umi{o.umi_location, o.umi_length, o.umi_skip, (uint8_t)o.umi_drop_comment,
+                                           (uint8_t)o.umi_not_trim, {0, 0}};
+            }
             lanes.back()->make(o, cyc0, (int)pack_n, stride0);
         }
         const double engines_ready_s = since(t0);

@@ -615,7 +615,8 @@ int fq_engine_set_gz_out(fq_engine* e, int32_t level);                  /* 0 (de
  * is the "left writer" of the rules above.  With an egress set, fq_engine_submit_text_routed also
  * takes -c (a pair with FQ_RF_CORRECTED on either record takes its sequence and quality bytes, the
  * merged read's included, from the corrected rows of the tile planes; names and strand lines always
- * come from the text) and -m --discard_unmerged; UMI is still refused.
+ * come from the text) and -m --discard_unmerged; UMI is taken once a UMI description is set
+ * (fq_engine_set_umi below) and refused without one.
  * fq_engine_set_egress (only while no pack is pending or enqueued, else FQ_E_INVALID): NULL (the
  * default) turns the routed egress off; fq_engine_submit_text, fq_engine_raw_begin and
  * fq_engine_raw_launch write and refuse as before (fq_engine_raw_begin takes -c and
@@ -660,6 +661,48 @@ typedef struct fq_raw_egress_out {
     uint64_t adapter_bytes[2]; /* set when the pack is reported by fq_engine_poll */
 } fq_raw_egress_out;
 int fq_engine_raw_launch_routed(fq_engine* e, fq_raw_result* r, fq_raw_egress_out* out, uint64_t seq_no);
+/* UMI (-u) on the routed egress.  The params' umi_front1/2 only cut the reads; the tag
+ * UmiProcessor::process builds and addTagToName puts into both mates' names (src/umiprocessor.cpp:10-89;
+ * fqtool_amd/host/processor.cpp umi_tag / tagged_name) is text, and the routed egress writes it once
+ * the engine has the description: location 1..6 (index1, index2, read1, read2, per_index, per_read),
+ * the UMI's length, the bases skipped after it, --umi_drop_comment and --umi_not_trim.  The tag is
+ * " OX:Z:" + umi and, when there is a quality part, " BZ:Z:" + qual: Read::firstIndex of the name(s)
+ * at locations 1, 2 and 5 (joined with '-' for a pair at 5), the first min(len, length) bases and
+ * their qualities at 3, 4 and 6 (location 4's quality part is bounded by read 1's length; location 6
+ * joins both reads' parts with '-', read 2's quality part taken after read 2's cut and bounded by
+ * read 1's cut length); always from the input text, also for a -c corrected pair.  A tag without a umi
+ * part is not added, nor is any at locations 2 and 4 on single-end input.  The tag goes in at the
+ * name's first blank (the rest is dropped with drop_comment) or at its end; the failure tag and the
+ * merged read's "_merged_<m1>_<m2>" then apply to the tagged name.  A FQ_RF_NULL read is written
+ * whole minus its UMI cut, min(length + skip, len - 1) bases.
+ * fq_engine_set_umi (only while no pack is pending or enqueued, and not inside a raw stream, else
+ * FQ_E_INVALID): NULL (the default) detaches the description and every call refuses UMI as before.
+ * A description is refused (FQ_E_INVALID) with a location outside 1..6, a length or skip that is
+ * negative or above 65535, length 0 at locations 3 / 4 / 6, a flag other than 0 / 1, or when the engine's umi_front1/2 are not what it implies:
+ * length + skip for read 1 at locations 3 and 6, for read 2 (paired) at 4 and 6, else 0, and 0 with
+ * not_trim.  With a description and an egress set, fq_engine_submit_text_routed, fq_engine_raw_begin
+ * and fq_engine_raw_launch_routed take UMI; fq_engine_submit_text and fq_engine_raw_launch keep
+ * refusing, and fq_engine_raw_begin refuses a description without an egress.
+ * fq_egress_bound_umi is the capacity the routed calls then check every open stream's buffer against
+ * (refusing before anything is launched, as for fq_egress_bound, which it equals for u == NULL):
+ *     fq_egress_bound(s, ...) + recs * add + names
+ * with recs = n records in OUT1 / OUT2 / UNPAIRED1 / UNPAIRED2 and 2 n (paired) in MERGED and FAILED,
+ * which may hold both mates (their own tags are in fq_egress_bound already);
+ * add = 12 + 2 * length at locations 3 and 4 (" OX:Z:", " BZ:Z:" and the two parts), 14 + 4 * length
+ * at 6 (two '-' more), names = 0; at locations 1 and 2 add = 6 (" OX:Z:") and names = (recs / n) *
+ * text_bytes1 (text_bytes2 at location 2), at location 5 add = 7 (a '-' more) and names = (recs / n) *
+ * (text_bytes1 + text_bytes2), since an index is part of a mate's name and the mate's text bytes
+ * bound all its names.  A stream whose bound passes 2^32 - 1 is refused (the cursors are 32-bit).
+ * The adapter entries of a routed raw pack are unchanged: an entry is at most 3 bytes plus bytes of
+ * the read at the record's ad_pos, which counts from the untrimmed read and so already lies past the
+ * UMI cut, so text_bytes[m] + 3 * pairs + 16 still bounds them. */
+typedef struct fq_umi {
+    int32_t location;      /* 1..6 */
+    int32_t length, skip;
+    uint8_t drop_comment, not_trim, reserved[2];
+} fq_umi;
+int fq_engine_set_umi(fq_engine* e, const fq_umi* u);
+size_t fq_egress_bound_umi(int32_t stream, uint64_t text_bytes1, uint64_t text_bytes2, uint64_t n, const fq_umi* u);
 
 /* ---- device inflate: BGZF input members inflated on the GPU ---------------------------------------
  * The mirror of device BGZF.  Every BGZF member is an independent raw deflate stream (RFC 1951)

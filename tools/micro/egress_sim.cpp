@@ -9,6 +9,9 @@
 //                                   n fq_text_rec}, then the fq_read_result records (n, or 2n for pairs).
 //                                   With correction_enabled the planes hold the rows as -c leaves them
 //                                   (fq_correct_pair_text applied to the FQ_RF_CORRECTED pairs).
+//                                   Magic 0x45475532: five more int32 follow the eight, the UMI description
+//                                   {location 1..6, length, skip, drop_comment, not_trim} (fq_umi), and the
+//                                   routine runs as the UMI instantiation of the kernels does.
 //                                   OUT: uint64 bytes[6], then the six streams' text.
 #include <stdint.h>
 #include <cstdio>
@@ -26,7 +29,10 @@ int main(int argc, char** argv) {
     FILE* f = fopen(argv[1], "rb");
     if (!f) return 2;
     int32_t h[8];
-    if (fread(h, 4, 8, f) != 8 || h[0] != 0x45475231) return 2;
+    if (fread(h, 4, 8, f) != 8 || (h[0] != 0x45475231 && h[0] != 0x45475532)) return 2;
+    const bool with_umi = h[0] == 0x45475532;
+    int32_t uh[5] = {0, 0, 0, 0, 0};
+    if (with_umi && (fread(uh, 4, 5, f) != 5 || uh[0] < 1 || uh[0] > 6 || uh[1] < 0 || uh[2] < 0)) return 2;
     const int paired = h[1], merge = h[2], discard = h[3], correction = h[4], n = h[6], stride = h[7];
     const uint32_t open = (uint32_t)h[5];
     if (n < 0 || stride <= 0 || (stride & 15) || (open >> FQ_EG_STREAMS)) return 2;
@@ -82,6 +88,10 @@ int main(int argc, char** argv) {
     }
     pk.res = res;
     pk.n = n, pk.stride = stride, pk.paired = paired, pk.merge = paired && merge, pk.discard = discard, pk.open = open;
+    pk.umi = Umi{uh[0], uh[1], uh[2], uh[3], uh[4]};
+    // (the tag is derived anew in each pass, as the two kernels do)
+    auto tag_of = [&](const Plan& p, const Mate* m) { return with_umi && p.n ? umi_tag(pk.umi, paired != 0, m) : Tag{}; };
+    auto load_pair = [&](int i, Mate(&m)[2], bool& planes) { return with_umi ? load<true>(pk, i, m, planes) : load(pk, i, m, planes); };
 
     // size pass, exclusive sums, exact buffers, write pass
     std::vector<uint32_t> size[FQ_EG_STREAMS], off[FQ_EG_STREAMS];
@@ -90,9 +100,9 @@ int main(int argc, char** argv) {
     for (int i = 0; i < n; ++i) {
         Mate m[2];
         bool planes;
-        const Plan p = load(pk, i, m, planes);
+        const Plan p = load_pair(i, m, planes);
         uint32_t z[FQ_EG_STREAMS];
-        sizes(p, m, z);
+        sizes(p, m, z, tag_of(p, m), uh[3] != 0);
         for (int s = 0; s < FQ_EG_STREAMS; ++s) {
             if (z[s] && !((open >> s) & 1u)) return 3;  // nothing may go to a stream without a writer
             size[s][(size_t)i] = z[s];
@@ -106,11 +116,11 @@ int main(int argc, char** argv) {
     for (int i = 0; i < n; ++i) {
         Mate m[2];
         bool planes;
-        const Plan p = load(pk, i, m, planes);
+        const Plan p = load_pair(i, m, planes);
         if (!p.n) continue;
         char* d[FQ_EG_STREAMS];
         for (int s = 0; s < FQ_EG_STREAMS; ++s) d[s] = ((open >> s) & 1u) ? out[s] + off[s][(size_t)i] : nullptr;
-        write(p, m, planes, d);
+        write(p, m, planes, d, tag_of(p, m), uh[3] != 0);
         for (int s = 0; s < FQ_EG_STREAMS; ++s)  // each cursor ends where the size pass said
             if (((open >> s) & 1u) && d[s] != out[s] + off[s][(size_t)i] + size[s][(size_t)i]) return 4;
     }
