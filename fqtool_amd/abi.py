@@ -318,6 +318,15 @@ def load_engine(path=ENGINE_LIB):
     lib.fq_kstat_read.argtypes = [vp, vp, ctypes.c_size_t]
     lib.fq_kstat_last_kernel_ms.argtypes = [vp]
     lib.fq_kstat_last_kernel_ms.restype = ctypes.c_double
+    lib.fq_ora_create.argtypes = [ctypes.c_int, i32, i32, i32, vp, vp, i32, vp, vp, i32, ctypes.POINTER(vp)]
+    lib.fq_ora_destroy.argtypes = [vp]
+    lib.fq_ora_reset.argtypes = [vp]
+    lib.fq_ora_words.argtypes = [vp]
+    lib.fq_ora_words.restype = ctypes.c_size_t
+    lib.fq_engine_set_ora.argtypes = [vp, vp]
+    lib.fq_ora_read.argtypes = [vp, vp, ctypes.c_size_t]
+    lib.fq_ora_last_kernel_ms.argtypes = [vp]
+    lib.fq_ora_last_kernel_ms.restype = ctypes.c_double
     lib.fq_deflate_bound.argtypes = [ctypes.c_size_t]
     lib.fq_deflate_bound.restype = ctypes.c_size_t
     lib.fq_deflate_code_lengths.argtypes = [vp, i32, i32, vp]
@@ -357,6 +366,8 @@ ENGINE_SYMBOLS = [
     "fq_inflate_create", "fq_inflate_destroy", "fq_inflate_members", "fq_inflate_bgzf", "fq_inflate_last_kernel_ms",
     "fq_kstat_create", "fq_kstat_destroy", "fq_kstat_reset", "fq_kstat_k", "fq_kstat_words", "fq_engine_set_kstat",
     "fq_kstat_read", "fq_kstat_last_kernel_ms",
+    "fq_ora_create", "fq_ora_destroy", "fq_ora_reset", "fq_ora_words", "fq_engine_set_ora", "fq_ora_read",
+    "fq_ora_last_kernel_ms",
 ]
 
 
@@ -385,6 +396,9 @@ def load_host(path=HOST_LIB):
     lib.fqh_session_set_dup.argtypes = [vp, vp, vp, vp]
     lib.fqh_session_kmer_params.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]
     lib.fqh_session_set_kmer.argtypes = [vp, vp]
+    lib.fqh_session_ora_params.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    lib.fqh_session_ora_hot_set.argtypes = [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(ci)]
+    lib.fqh_session_set_ora.argtypes = [vp, vp, cs]
     lib.fqh_session_finish.argtypes = [vp]
     lib.fqh_session_finish.restype = vp
     lib.fqh_session_close.argtypes = [vp]
@@ -407,5 +421,6 @@ HOST_SYMBOLS = [
     "fqh_session_next", "fqh_session_consume", "fqh_session_add_acc", "fqh_session_finish",
     "fqh_session_close", "fqh_debug_records", "fqh_session_dup_params", "fqh_session_set_dup",
     "fqh_session_kmer_params", "fqh_session_set_kmer",
+    "fqh_session_ora_params", "fqh_session_ora_hot_set", "fqh_session_set_ora",
     "fqh_set_kmer_backend", "fqh_pargz_read_all", "fqh_gzread_all", "fqh_gz_drain",
 ]

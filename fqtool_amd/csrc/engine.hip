@@ -124,6 +124,7 @@ struct fq_engine {
     int raw_prev_slot = -1;
     fq_dup* dup = nullptr;    // duplication table fed by every pack (-d)
     fq_kstat* kstat = nullptr;  // k-mer tables fed by every pack (--kmer)
+    fq_ora* ora = nullptr;      // overrepresented-sequence counts fed by every pack (--ora)
     // device BGZF (fq_engine_set_gz_out): level 1..9, 0 = off; the compressor's scratch, one per
     // engine (its launches all run on the compute stream, one after another)
     int gz_level = 0;
@@ -389,6 +390,12 @@ static int launch(fq_engine* e, const fq_batch& db, fq_read_result* dres, hipStr
         if (rc == FQ_OK) rc = fq_kstat_pre(e->kstat, db, e->p, s);
         if (rc != FQ_OK) return fail(e, rc, std::string("k-mer statistics: ") + fq_kstat_error(e->kstat));
     }
+    if (e->ora) {  // likewise the pre-filter overrepresented sequences
+        int rc = FQ_OK;
+        if (!dres) rc = fq_ora_records(e->ora, (size_t)db.n * (e->p.paired ? 2 : 1), s, &dres);
+        if (rc == FQ_OK) rc = fq_ora_pre(e->ora, db, e->p, s);
+        if (rc != FQ_OK) return fail(e, rc, std::string("overrepresented sequences: ") + fq_ora_error(e->ora));
+    }
     // (index-filtered pairs are handed to the general kernel one by one)
     if (e->fast) {
         // hand-off list: pair / read indices, reserved a tile's worth (<= 64) at a time, at most
@@ -416,6 +423,10 @@ static int launch(fq_engine* e, const fq_batch& db, fq_read_result* dres, hipStr
     if (e->kstat) {  // the post-filter k-mers, from the records the kernels above have written
         const int rc = fq_kstat_post(e->kstat, db, e->p, dres, s);
         if (rc != FQ_OK) return fail(e, rc, std::string("k-mer statistics: ") + fq_kstat_error(e->kstat));
+    }
+    if (e->ora) {  // and the post-filter overrepresented sequences
+        const int rc = fq_ora_post(e->ora, db, e->p, dres, s);
+        if (rc != FQ_OK) return fail(e, rc, std::string("overrepresented sequences: ") + fq_ora_error(e->ora));
     }
     return FQ_OK;
 }
@@ -1479,6 +1490,19 @@ int fq_engine_set_kstat(fq_engine* e, fq_kstat* h) {
     HIP_TRY(e, hipSetDevice(e->device));
     HIP_TRY(e, hipDeviceSynchronize());  // packs in flight finish with the old tables
     e->kstat = h;
+    return FQ_OK;
+}
+
+int fq_engine_set_ora(fq_engine* e, fq_ora* h) {
+    if (!e) return FQ_E_INVALID;
+    if (h) {
+        int dev = -1;
+        if (fq_ora_device(h, &dev) != FQ_OK || dev != e->device)
+            return fail(e, FQ_E_INVALID, "the overrepresented-sequence counts are on another device");
+    }
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipDeviceSynchronize());  // packs in flight finish with the old handle
+    e->ora = h;
     return FQ_OK;
 }
 

@@ -48,6 +48,13 @@ int fq_kstat_post(fq_kstat* h, const fq_batch& b, const fq_params& p, const fq_r
 int fq_kstat_records(fq_kstat* h, size_t n, hipStream_t s, fq_read_result** out);
 const char* fq_kstat_error(const fq_kstat* h);
 int fq_kstat_device(const fq_kstat* h, int* device);
+// overrepresented sequences of one pack (ora.hip): two passes placed like the k-mer ones, and a
+// record buffer lent likewise
+int fq_ora_pre(fq_ora* h, const fq_batch& b, const fq_params& p, hipStream_t s);
+int fq_ora_post(fq_ora* h, const fq_batch& b, const fq_params& p, const fq_read_result* res, hipStream_t s);
+int fq_ora_records(fq_ora* h, size_t n, hipStream_t s, fq_read_result** out);
+const char* fq_ora_error(const fq_ora* h);
+int fq_ora_device(const fq_ora* h, int* device);
 // FASTQ-text packs (text.hip): tile planes built from the text; output text of the passing records
 hipError_t fq_launch_text_tiles(const char* d_text, const fq_text_rec* d_rec, int n, int stride, uint8_t* seq,
                                 uint8_t* qual, uint16_t* lens, hipStream_t s);

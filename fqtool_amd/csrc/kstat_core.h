@@ -141,33 +141,60 @@ FQ_KSTAT_HD void count_merged(const kstat_row& a, int st1, int m1, const kstat_r
 // are discarded; without -m both mates count when both pass.  A mate that trimAndCut dropped
 // (FQ_RF_NULL) keeps the pair out, index-filtered pairs never get here.  Windows that do not lie
 // inside the read (a record of a pack that failed) are skipped, never read.
-// emit1 / emit2 take the post-R1 / post-R2 keys.
-template <class Emit1, class Emit2>
-FQ_KSTAT_HD void post_pair(int merge_enabled, int discard_unmerged, const fq_read_result& r1, const fq_read_result& r2,
-                           const kstat_row& s1, int l1, const kstat_row& s2, int l2, int k, Emit1& emit1, Emit2& emit2) {
+// The visitor takes them in the reference's order: v.row1(start, len) / v.merged(st1, m1, st2, m2)
+// go to post-R1, v.row2(start, len) to post-R2 (ora_core.h walks the same reads).
+template <class Visit>
+FQ_KSTAT_HD void visit_post_pair(int merge_enabled, int discard_unmerged, const fq_read_result& r1, const fq_read_result& r2,
+                                 int l1, int l2, Visit& v) {
     if ((r1.flags | r2.flags) & (FQ_RF_NULL | FQ_RF_INDEX_FILTERED)) return;
     if ((int)r1.start + (int)r1.len > l1 || (int)r2.start + (int)r2.len > l2) return;
     if (merge_enabled) {
         if (r1.flags & FQ_RF_MERGED) {
             if (r1.code != FQ_PASS_FILTER || r1.m_len1 > r1.len || r1.m_len2 > r2.len) return;
-            count_merged(s1, r1.start, r1.m_len1, s2, r2.start, r1.m_len2, k, emit1);
+            v.merged(r1.start, r1.m_len1, r2.start, r1.m_len2);
         } else if (!discard_unmerged) {
-            if (r1.code == FQ_PASS_FILTER) count_row(s1, r1.start, r1.len, k, emit1);
-            if (r2.code == FQ_PASS_FILTER) count_row(s2, r2.start, r2.len, k, emit2);
+            if (r1.code == FQ_PASS_FILTER) v.row1(r1.start, r1.len);
+            if (r2.code == FQ_PASS_FILTER) v.row2(r2.start, r2.len);
         }
         return;
     }
     if (r1.code != FQ_PASS_FILTER || r2.code != FQ_PASS_FILTER) return;
-    count_row(s1, r1.start, r1.len, k, emit1);
-    count_row(s2, r2.start, r2.len, k, emit2);
+    v.row1(r1.start, r1.len);
+    v.row2(r2.start, r2.len);
 }
 
 // single end (reference src/seprocessor.cpp:339-345)
-template <class Emit>
-FQ_KSTAT_HD void post_single(const fq_read_result& r, const kstat_row& s, int l, int k, Emit& emit) {
+template <class Visit>
+FQ_KSTAT_HD void visit_post_single(const fq_read_result& r, int l, Visit& v) {
     if (r.flags & (FQ_RF_NULL | FQ_RF_INDEX_FILTERED)) return;
     if (r.code != FQ_PASS_FILTER || (int)r.start + (int)r.len > l) return;
-    count_row(s, r.start, r.len, k, emit);
+    v.row1(r.start, r.len);
+}
+
+// the k-mers of those reads: emit1 / emit2 take the post-R1 / post-R2 keys
+template <class Emit1, class Emit2>
+struct kstat_post_count {
+    const kstat_row& s1;
+    const kstat_row& s2;
+    int k;
+    Emit1& emit1;
+    Emit2& emit2;
+    FQ_KSTAT_HD void row1(int start, int len) { count_row(s1, start, len, k, emit1); }
+    FQ_KSTAT_HD void row2(int start, int len) { count_row(s2, start, len, k, emit2); }
+    FQ_KSTAT_HD void merged(int st1, int m1, int st2, int m2) { count_merged(s1, st1, m1, s2, st2, m2, k, emit1); }
+};
+
+template <class Emit1, class Emit2>
+FQ_KSTAT_HD void post_pair(int merge_enabled, int discard_unmerged, const fq_read_result& r1, const fq_read_result& r2,
+                           const kstat_row& s1, int l1, const kstat_row& s2, int l2, int k, Emit1& emit1, Emit2& emit2) {
+    kstat_post_count<Emit1, Emit2> v{s1, s2, k, emit1, emit2};
+    visit_post_pair(merge_enabled, discard_unmerged, r1, r2, l1, l2, v);
+}
+
+template <class Emit>
+FQ_KSTAT_HD void post_single(const fq_read_result& r, const kstat_row& s, int l, int k, Emit& emit) {
+    kstat_post_count<Emit, Emit> v{s, s, k, emit, emit};
+    visit_post_single(r, l, v);
 }
 
 }  // namespace fqkstat

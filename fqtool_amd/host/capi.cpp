@@ -196,6 +196,35 @@ int fqh_session_set_kmer(fqh_session* s, const uint64_t* tables) {
     return 0;
 }
 
+// --ora: the sampling (0 without --ora) and the two evaluated lengths; the hot sets the pre-pass
+// chose (which 0: the read-1 Stats', 1: the read-2 Stats'; *off has *n + 1 entries); and the
+// caller's four blocks [pre-R1 | pre-R2 | post-R1 | post-R2] (include/fqengine.h fq_ora_read)
+int fqh_session_ora_params(fqh_session* s, int* enabled, int* sampling, int* eval_len1, int* eval_len2) {
+    *enabled = s->o.ora;
+    *sampling = s->o.ora_sampling();
+    *eval_len1 = s->o.est_seq_len1;
+    *eval_len2 = s->o.est_seq_len2;
+    return 0;
+}
+
+int fqh_session_ora_hot_set(fqh_session* s, int which, const uint8_t** seq, const uint32_t** off, int* n) {
+    if (which < 0 || which > 1) return -1;
+    const Options::HotSet& h = s->o.ora_set[which];
+    *seq = reinterpret_cast<const uint8_t*>(h.bytes.data());
+    *off = h.off.data();
+    *n = h.size();
+    return 0;
+}
+
+int fqh_session_set_ora(fqh_session* s, const uint64_t* blocks, size_t words) {
+    if (!s->o.ora) return -1;
+    HostAcc probe;
+    probe.set_ora(s->o, std::vector<uint64_t>());
+    if (words != probe.ora_words() || (words && !blocks)) return -1;
+    s->acc.set_ora(s->o, std::vector<uint64_t>(blocks, blocks + words));
+    return 0;
+}
+
 int fqh_session_add_acc(fqh_session* s, const uint64_t* acc, int max_cycles) {
     s->acc.add(acc, max_cycles);
     return 0;

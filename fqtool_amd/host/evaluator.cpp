@@ -10,8 +10,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <map>
 #include <memory>
 #include <sstream>
+#include <string_view>
+#include <unordered_map>
+#include <utility>
+#include <vector>
 
 #include "fastq.h"
 #include "../../include/fqhost.h"
@@ -297,6 +302,92 @@ std::string detect_adapter(const std::string& path, int trim_tail1, std::string*
         if (!est.empty()) return est;
     }
     return "";
+}
+
+// Evaluator::computeOverRepSeq, src/evaluator.cpp:120-189.  The reference counts every substring in
+// a std::map<string>; here each step's windows are hashed, sorted by hash and only the groups large
+// enough to matter are compared byte by byte, which gives the same counts.  The selection and the
+// substring elimination (in map order, against the map as it stands during the erase loop, with
+// the integer division) give the reference's result.
+void compute_overrep(const std::string& path, Options::HotSet& out) {
+    out = Options::HotSet();
+    const size_t kBaseLimit = 151 * 10000;
+    FqReader r(path, false);
+    std::string n, s, d, q;
+    std::string text;                // the reads back to back
+    std::vector<uint32_t> off{0};
+    size_t bases = 0;
+    while (bases < kBaseLimit && r.read(n, s, d, q)) {
+        bases += s.size();
+        text += s;
+        off.push_back((uint32_t)text.size());
+    }
+    // kept when (length >= 150 and count >= 3) or (>= 100 and >= 5) or (>= 40 and >= 20) or
+    // (>= 20 and >= 100) or (>= 10 and >= 500): the smallest count that keeps a length
+    auto keep_from = [](int len) { return len >= 150 ? 3u : len >= 100 ? 5u : len >= 40 ? 20u : len >= 20 ? 100u : 500u; };
+    std::map<std::string, size_t> hot;
+    std::vector<std::pair<uint64_t, uint32_t>> win;  // (hash of the window, its start in text)
+    for (int step : {10, 20, 40, 100, 149}) {
+        win.clear();
+        for (size_t k = 0; k + 1 < off.size(); ++k)
+            for (uint32_t i = off[k]; i + (uint32_t)step < off[k + 1]; ++i) {  // i < rlen - step
+                uint64_t h = 1469598103934665603ull;
+                for (int b = 0; b < step; ++b) h = (h ^ (uint8_t)text[i + (uint32_t)b]) * 1099511628211ull;
+                win.emplace_back(h, i);
+            }
+        std::sort(win.begin(), win.end());
+        const size_t need = keep_from(step);
+        for (size_t a = 0, b; a < win.size(); a = b) {
+            for (b = a + 1; b < win.size() && win[b].first == win[a].first; ++b) {}
+            if (b - a < need) continue;
+            // windows of one hash: equal bytes almost surely, but the count is of equal bytes only
+            std::sort(win.begin() + (long)a, win.begin() + (long)b, [&](const auto& x, const auto& y) {
+                return text.compare(x.second, (size_t)step, text, y.second, (size_t)step) < 0;
+            });
+            for (size_t c = a, e; c < b; c = e) {
+                for (e = c + 1; e < b && text.compare(win[e].second, (size_t)step, text, win[c].second, (size_t)step) == 0; ++e) {}
+                if (e - c >= need) hot[text.substr(win[c].second, (size_t)step)] = e - c;
+            }
+        }
+    }
+    // The erase loop (src/evaluator.cpp:166-188): in map order a sequence goes when a DIFFERENT hot
+    // sequence still in the map contains it and count / count2 < 10.  A container is longer, so
+    // instead of running find() over all pairs (quadratic: 18.7 k hot 100-mers on real data), the
+    // windows of every member at the shorter hot lengths are looked up once; a sequence's containers
+    // are then checked against what the loop has erased so far, which is the reference's outcome.
+    std::vector<const std::pair<const std::string, size_t>*> member;
+    std::unordered_map<std::string_view, size_t> index;  // sequence (a view of the map's key) -> its position in map order
+    std::vector<size_t> lens;
+    for (const auto& e : hot) {
+        index.emplace(std::string_view(e.first), member.size());
+        member.push_back(&e);
+        if (std::find(lens.begin(), lens.end(), e.first.size()) == lens.end()) lens.push_back(e.first.size());
+    }
+    std::vector<std::vector<uint32_t>> containers(member.size());
+    for (size_t c = 0; c < member.size(); ++c) {
+        const std::string& big = member[c]->first;
+        for (size_t len : lens) {
+            if (len >= big.size()) continue;
+            for (size_t i = 0; i + len <= big.size(); ++i) {
+                const auto f = index.find(std::string_view(big).substr(i, len));
+                if (f != index.end() && (containers[f->second].empty() || containers[f->second].back() != (uint32_t)c))
+                    containers[f->second].push_back((uint32_t)c);
+            }
+        }
+    }
+    std::vector<char> gone(member.size(), 0);
+    for (size_t k = 0; k < member.size(); ++k)
+        for (uint32_t c : containers[k])
+            if (!gone[c] && member[k]->second / member[c]->second < 10) {
+                gone[k] = 1;
+                break;
+            }
+    for (size_t k = 0; k < member.size(); ++k)
+        if (gone[k]) hot.erase(member[k]->first);
+    for (const auto& e : hot) {
+        out.bytes += e.first;
+        out.off.push_back((uint32_t)out.bytes.size());
+    }
 }
 
 void set_kmer_backend(const fqh_kmer_backend* b) {

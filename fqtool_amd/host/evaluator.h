@@ -5,6 +5,7 @@
 #include <string>
 
 #include "../../include/fqhost.h"
+#include "options.h"
 
 namespace fqhost {
 
@@ -20,5 +21,8 @@ int evaluate_read_num(const std::string& path);
 // given to set_kmer_backend.
 std::string detect_adapter(const std::string& path, int trim_tail1, std::string* msgs = nullptr, int device = 0);
 void set_kmer_backend(const struct fqh_kmer_backend* b);
+// Evaluator::computeOverRepSeq (src/evaluator.cpp:120-189): the hot sequences of one input file,
+// in std::map order (the counts of the pre-pass itself are not kept: Stats starts them at 0)
+void compute_overrep(const std::string& path, struct Options::HotSet& out);
 
 }  // namespace fqhost

@@ -270,6 +270,88 @@ HNode stats_kmer(const Summary& st, const std::string& filtering, const std::str
     return sec;
 }
 
+// Stats::reportHtmlORA, src/stats.cpp:445-548
+HNode stats_ora(const Summary& st, const std::string& filtering, const std::string& read) {
+    const std::string sub = filtering + ": " + read + ": overrepresented sequences";
+    const std::string div = replace_all(replace_all(sub, " ", "_"), ":", "_");
+    HNode sec("div.section_div");
+    HNode title("div.subsection_title");
+    HNode link("a", sub);
+    link.attr("title", "click to hide/show");
+    link.attr("onclick", "showOrHide('" + div + "')");
+    title.add(link);
+    sec.add(title);
+    HNode id("div#" + div);
+    id.add(HNode("div.sub_section_tips", "Sampling rate: 1/" + std::to_string(st.ora_sampling)));
+    HNode table("table.summary_table");
+    HNode head("tr");
+    head.attr("style", "font-weight:bold;");
+    head.add(HNode("td", "overrepresented sequence"));
+    head.add(HNode("td", "count (% of bases)"));
+    head.add(HNode("td", "distribution: cycle 1 ~ cycle " + std::to_string(st.ora_eval)));
+    table.add(head);
+    const double bases = (double)st.bases;
+    int found = 0;
+    std::string js = "var seqlen = " + std::to_string(st.ora_eval) + ";\nvar orp_dist = {\n";
+    for (const auto& e : st.ora) {
+        const std::string& seq = e.first;
+        const uint64_t count = e.second[0];
+        if (!st.ora_passed(seq, count)) continue;
+        const double percent = (100.0 * count * seq.size() * st.ora_sampling) / bases;
+        HNode row("tr");
+        HNode col1("td", seq);
+        col1.attr("width", "400").attr("style", "word-break:break-all;font-size:8px;");
+        HNode col2("td", std::to_string(count) + "(" + fstr(percent) + "%)");
+        col2.attr("width", "200");
+        HNode col3("td");
+        col3.attr("width", "250");
+        HNode canvas("canvas#" + div + "_" + seq);
+        canvas.close = false;
+        canvas.attr("width", "240").attr("height", "20");
+        col3.add(canvas);
+        row.add(col1).add(col2).add(col3);
+        table.add(row);
+        if (found++) js += ",\n";
+        js += "\t\"" + div + "_" + seq + "\":[" + list2string(e.second + 1, st.ora_eval) + "]";
+    }
+    if (found == 0) {
+        HNode row("tr");
+        HNode col("td", "not found");
+        col.attr("style", "text-align:center").attr("colspan", "3");
+        row.add(col);
+        table.add(row);
+    }
+    id.add(table);
+    js += "\n};\n"
+          "for (seq in orp_dist) {\n"
+          "    var cvs = document.getElementById(seq);\n"
+          "    var ctx = cvs.getContext('2d'); \n"
+          "    var data = orp_dist[seq];\n"
+          "    var w = 240;\n"
+          "    var h = 20;\n"
+          "    ctx.fillStyle='#cccccc';\n"
+          "    ctx.fillRect(0, 0, w, h);\n"
+          "    ctx.fillStyle='#0000FF';\n"
+          "    var maxVal = 0;\n"
+          "    for(d=0; d<seqlen; d++) {\n"
+          "        if(data[d]>maxVal) maxVal = data[d];\n"
+          "    }\n"
+          "    var step = (seqlen-1) /  (w-1);\n"
+          "    for(x=0; x<w; x++){\n"
+          "        var target = step * x;\n"
+          "        var val = data[Math.floor(target)];\n"
+          "        var y = Math.floor((val / maxVal) * h);\n"
+          "        ctx.fillRect(x,h-1, 1, -y);\n"
+          "    }\n"
+          "}\n";
+    HNode script("script");
+    script.attr("language", "javascript");
+    script.add_text(js);
+    sec.add(id);
+    sec.add(script);
+    return sec;
+}
+
 // Stats::reportHtmlContents, src/stats.cpp:716-806
 HNode stats_contents(const Summary& st, const std::string& filtering, const std::string& read) {
     const std::string sub = filtering + ": " + read + ": base contents";
@@ -646,9 +728,11 @@ std::string build_html(const Options& o, const HostAcc& a, const AdapterCounts& 
     HNode pre_div("div#before_filtering");
     pre_div.add(stats_quality(pre1, "Before filtering", "read1")).add(stats_contents(pre1, "Before filtering", "read1"));
     if (pre1.kmer_k) pre_div.add(stats_kmer(pre1, "Before filtering", "read1"));
+    if (pre1.ora_sampling) pre_div.add(stats_ora(pre1, "Before filtering", "read1"));
     if (pe) {
         pre_div.add(stats_quality(pre2, "Before filtering", "read2")).add(stats_contents(pre2, "Before filtering", "read2"));
         if (pre2.kmer_k) pre_div.add(stats_kmer(pre2, "Before filtering", "read2"));
+        if (pre2.ora_sampling) pre_div.add(stats_ora(pre2, "Before filtering", "read2"));
     }
     body.add(pre_sec);
     body.add(pre_div);
@@ -662,9 +746,11 @@ std::string build_html(const Options& o, const HostAcc& a, const AdapterCounts& 
     HNode post_div("div#after_filtering");
     post_div.add(stats_quality(post1, "After filtering", "read1")).add(stats_contents(post1, "After filtering", "read1"));
     if (post1.kmer_k) post_div.add(stats_kmer(post1, "After filtering", "read1"));
+    if (post1.ora_sampling) post_div.add(stats_ora(post1, "After filtering", "read1"));
     if (pe) {
         post_div.add(stats_quality(post2, "After filtering", "read2")).add(stats_contents(post2, "After filtering", "read2"));
         if (post2.kmer_k) post_div.add(stats_kmer(post2, "After filtering", "read2"));
+        if (post2.ora_sampling) post_div.add(stats_ora(post2, "After filtering", "read2"));
     }
     post_sec.add(post_div);
     body.add(post_sec);

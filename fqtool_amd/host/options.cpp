@@ -177,9 +177,15 @@ Table make_table(Options& o) {
     range(t.add({"--umi_skip_length"}, Kind::Int, &o.umi_skip, "bases to skip after umi"), 0, 1000).needs = {"-u"};
     t.add({"--umi_drop_comment"}, Kind::Flag, &o.umi_drop_comment, "drop other comment information").needs = {"-u"};
     t.add({"--umi_not_trim"}, Kind::Flag, &o.umi_not_trim, "do not trim reads").needs = {"-u"};
-    // ---- ORA (outside scope) / k-mer
-    t.add({"--ora"}, Kind::Flag, &t.dummy_bool, "enable ORA").unsupported = true;
-    range(t.add({"--ora_sample"}, Kind::Int, &t.dummy_int, "ORA sampling steps"), 1, 10000).needs = {"--ora"};
+    // ---- ORA (opt-in: honoured with FQ_ORA=1 in the environment, refused without) / k-mer
+    const char* ora_env = std::getenv("FQ_ORA");
+    if (ora_env && std::string(ora_env) == "1") {
+        t.add({"--ora"}, Kind::Flag, &o.ora, "enable ORA");
+        range(t.add({"--ora_sample"}, Kind::Int, &o.ora_sample, "ORA sampling steps"), 1, 10000).needs = {"--ora"};
+    } else {
+        t.add({"--ora"}, Kind::Flag, &t.dummy_bool, "enable ORA").unsupported = true;
+        range(t.add({"--ora_sample"}, Kind::Int, &t.dummy_int, "ORA sampling steps"), 1, 10000).needs = {"--ora"};
+    }
     t.add({"--kmer"}, Kind::Flag, &o.kmer, "enable kmer analysis");
     range(t.add({"--kmer_length"}, Kind::Int, &o.kmer_length, "kmer length to analysis"), 4, 16).needs = {"--kmer"};
     // ---- reporting / system

@@ -2,8 +2,9 @@
 //
 // Mirrors the reference's Options tree (src/options.h:15-386), its CLI (src/main.cpp:18-120,
 // CLI11 1.7.1 semantics: bool flags reset to false at registration, range checks, needs /
-// excludes), and Options::update / validate (src/options.cpp:24-71).  ORA (outside this build's
-// scope) is parsed and rejected with a clear message instead of being silently ignored.
+// excludes), and Options::update / validate (src/options.cpp:24-71).  ORA is opt-in: with FQ_ORA=1
+// in the environment --ora / --ora_sample are honoured, without it they are parsed and rejected
+// with a clear message instead of being silently ignored.
 #pragma once
 
 #include <cstdint>
@@ -69,6 +70,19 @@ struct Options {
     bool kmer = false;
     int kmer_length = 0;
     int kmer_k() const { return kmer ? kmer_length : 0; }  // the effective length (Stats::mKmerLen)
+    // --ora / --ora_sample (honoured with FQ_ORA=1 only): the sampling defaults to 20
+    // (src/options.h:158); the hot sets are the evaluator's (compute_overrep), set 0 for the read-1
+    // Stats and set 1 for the read-2 Stats, each in std::map order: sequence i = bytes[off[i], off[i + 1])
+    struct HotSet {
+        std::string bytes;
+        std::vector<uint32_t> off{0};
+        int size() const { return (int)off.size() - 1; }
+        std::string seq(int i) const { return bytes.substr(off[(size_t)i], off[(size_t)i + 1] - off[(size_t)i]); }
+    };
+    bool ora = false;
+    int ora_sample = 20;
+    HotSet ora_set[2];
+    int ora_sampling() const { return ora ? ora_sample : 0; }  // Stats::mOverRepSampling
     bool split() const { return split_by_number || split_by_lines; }
     // leading bases UmiProcessor::process trims from mate m (before clamping to the read length)
     int umi_front(int m) const {

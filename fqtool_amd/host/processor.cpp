@@ -47,6 +47,12 @@
 #pragma weak fq_kstat_words
 #pragma weak fq_kstat_read
 #pragma weak fq_engine_set_kstat
+// ... and the overrepresented-sequence counts (FQ_ORA=1 --ora)
+#pragma weak fq_ora_create
+#pragma weak fq_ora_destroy
+#pragma weak fq_ora_words
+#pragma weak fq_ora_read
+#pragma weak fq_engine_set_ora
 
 namespace fqhost {
 namespace {
@@ -1430,11 +1436,13 @@ struct Lane {
         if (e) fq_engine_destroy(e);
         if (dup) fq_dup_destroy(dup);
         if (kstat) fq_kstat_destroy(kstat);
+        if (ora) fq_ora_destroy(ora);
     }
     int dev, depth;
     fq_engine* e = nullptr;
     fq_dup* dup = nullptr;  // -d: this engine's table, kept across re-creation
     fq_kstat* kstat = nullptr;  // --kmer: this engine's k-mer tables, kept likewise
+    fq_ora* ora = nullptr;      // --ora: the run's overrepresented-sequence counts (its one engine's), kept likewise
     int gz_level = 0;       // FQ_GZ_DEVICE=1 with .gz outputs: text / raw packs come back as BGZF members
     bool routed = false;    // routed egress: text packs come back as the Sink's writers' streams
     uint32_t eg_open = 0;   // ... those writers, as FQ_EG_* bits
@@ -1479,6 +1487,17 @@ struct Lane {
                                          std::to_string(o.kmer_k()) + ") failed");
             if (fq_engine_set_kstat(e, kstat) != FQ_OK)
                 throw std::runtime_error(std::string("fq_engine_set_kstat: ") + fq_engine_last_error(e));
+        }
+        if (o.ora) {
+            if (!fq_ora_create || !fq_ora_destroy || !fq_ora_words || !fq_ora_read || !fq_engine_set_ora)
+                throw std::runtime_error("--ora: this engine library has no overrepresented-sequence counting (fq_ora_*)");
+            const Options::HotSet &s1 = o.ora_set[0], &s2 = o.ora_set[1];
+            if (!ora && fq_ora_create(dev, o.ora_sample, o.est_seq_len1, o.est_seq_len2,
+                                      reinterpret_cast<const uint8_t*>(s1.bytes.data()), s1.off.data(), s1.size(),
+                                      reinterpret_cast<const uint8_t*>(s2.bytes.data()), s2.off.data(), s2.size(), &ora) != FQ_OK)
+                throw std::runtime_error("fq_ora_create (device " + std::to_string(dev) + ") failed");
+            if (fq_engine_set_ora(e, ora) != FQ_OK)
+                throw std::runtime_error(std::string("fq_engine_set_ora: ") + fq_engine_last_error(e));
         }
         if (gz_level && fq_engine_set_gz_out(e, gz_level) != FQ_OK)
             throw std::runtime_error(std::string("fq_engine_set_gz_out: ") + fq_engine_last_error(e));
@@ -2336,6 +2355,13 @@ Options prepare_options(int argc, char** argv, bool detect_adapters) {
     // Evaluator pre-pass, src/main.cpp:126-143
     if (!o.in1.empty()) o.est_seq_len1 = evaluate_read_len(o.in1);
     if (!o.in2.empty()) o.est_seq_len2 = evaluate_read_len(o.in2);
+    if (o.ora) {  // Evaluator::evaluateOverRepSeqs, src/main.cpp:136-138 (an interleaved input's mates all go to set 1)
+        // (the reference's Stats throws std::out_of_range building its step set when evalLen - 2 < 1)
+        if (o.est_seq_len1 < 3 || o.est_seq_len2 < 3)
+            throw std::runtime_error("--ora needs reads of at least 3 bases in the first 1000 records of each input");
+        if (!o.in1.empty()) compute_overrep(o.in1, o.ora_set[0]);
+        if (!o.in2.empty()) compute_overrep(o.in2, o.ora_set[1]);
+    }
     if (o.split_by_number) {  // evaluateReadNum + the split size, src/main.cpp:130-134
         o.est_reads_num = evaluate_read_num(o.in1);
         if (o.split_number == 0) throw std::runtime_error("--split_file_number must be given (non-zero) with -s");
@@ -2431,7 +2457,11 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
         // (raw streams: packs of 128 Ki pairs keep six windows' copies queued in 48 MiB windows)
         const size_t pack_n = o.pack_pairs ? o.pack_pairs : std::max<size_t>(o.max_reads_in_pack, 131072);
         int est = std::max(o.est_seq_len1, paired ? o.est_seq_len2 : 0);
-        const std::vector<int> devices = o.device_list();
+        std::vector<int> devices = o.device_list();
+        // --ora: the post-filter Stats sample by a read's number in the whole stream, which one
+        // engine's handle counts on the device; the run uses the first device only
+        const int ora_devices_given = (int)devices.size();
+        if (o.ora) devices.resize(1);
         const int G = (int)devices.size();
         const int depth = G > 2 ? 2 : 3;  // packs in flight per engine (each holds a device slot)
         // -w host threads (the reference's worker count) pack tiles, format and compress
@@ -2774,6 +2804,11 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
                 acc.add_kmer(o.kmer_k(), buf.data());
             }
         }
+        if (o.ora) {
+            std::vector<uint64_t> buf(fq_ora_words(lanes[0]->ora));
+            if (fq_ora_read(lanes[0]->ora, buf.data(), buf.size()) != FQ_OK) throw std::runtime_error("fq_ora_read failed");
+            acc.set_ora(o, buf);
+        }
         outs.close();
         double detect_s = 0;
         if (det.valid()) {
@@ -2829,7 +2864,10 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
             " s, engines ready at " + std::to_string(engines_ready_s) + " s, first pack submitted at " +
             std::to_string(lanes[0]->first_submit) + " s, pipeline done at " +
             std::to_string(pipeline_done_s) +
-            " s; JSON report " + o.json_file + ", HTML report " + o.html_file);
+            " s; JSON report " + o.json_file + ", HTML report " + o.html_file +
+            (o.ora && ora_devices_given > 1 ? "; --ora: one engine on device " + std::to_string(devices[0]) + " of the " +
+                                                  std::to_string(ora_devices_given) + " given (the sampling counts one stream)"
+                                            : std::string()));
         if (std::getenv("FQ_TIMING_MONO")) {  // (profiling: steady-clock stamps, to time exec and exit from outside)
             auto mono = [](std::chrono::steady_clock::time_point t) {
                 return std::to_string(std::chrono::duration<double>(t.time_since_epoch()).count());

@@ -280,6 +280,17 @@ Summary summarize(const HostAcc& a, int k) {
         for (size_t i = 0; i < (size_t)1 << (2 * s.kmer_k); ++i) km[kmer_text(i, s.kmer_k)] = Json::s(std::to_string(s.kmer[i]));
         s.json["KmerCount"] = km;
     }
+    if (a.ora_sampling) {  // src/stats.cpp:419-428: the sequences that pass overRepPassed, null when none does
+        s.ora_sampling = a.ora_sampling;
+        s.ora_eval = a.ora_eval[k & 1];
+        const Options::HotSet& set = a.ora_set[k & 1];
+        Json ora;
+        for (int i = 0; i < set.size(); ++i) {
+            s.ora.emplace_back(set.seq(i), a.ora_row(k, i));
+            if (s.ora_passed(s.ora.back().first, s.ora.back().second[0])) ora[s.ora.back().first] = Json::u(s.ora.back().second[0]);
+        }
+        s.json["OverrepresentedSequences"] = ora;
+    }
     return s;
 }
 

@@ -54,6 +54,27 @@ class HostAcc {
     const uint64_t* kmer_table(int stats_block) const { return kmer.data() + ((size_t)stats_block << (2 * kmer_k)); }
     int kmer_k = 0;  // 0: no k-mer counting
     std::vector<uint64_t> kmer;
+    // --ora: the run's hot sets (set 0: the read-1 Stats, set 1: the read-2 Stats) and the four blocks
+    // [pre-R1 | pre-R2 | post-R1 | post-R2] of n x (1 + evalLen) counters (include/fqengine.h fq_ora_read)
+    void set_ora(const Options& o, const std::vector<uint64_t>& blocks) {
+        ora_sampling = o.ora_sampling();
+        ora_eval[0] = o.est_seq_len1, ora_eval[1] = o.est_seq_len2;
+        ora_set[0] = o.ora_set[0], ora_set[1] = o.ora_set[1];
+        ora = blocks;
+        ora.resize(ora_words(), 0);
+    }
+    size_t ora_block_words(int set) const { return (size_t)ora_set[set].size() * (size_t)(1 + ora_eval[set]); }
+    size_t ora_words() const { return 2 * (ora_block_words(0) + ora_block_words(1)); }
+    // sequence i's count and distribution in Stats block k
+    const uint64_t* ora_row(int stats_block, int i) const {
+        const size_t w0 = ora_block_words(0), w1 = ora_block_words(1);
+        const size_t first[4] = {0, w0, w0 + w1, 2 * w0 + w1};
+        return ora.data() + first[stats_block] + (size_t)i * (size_t)(1 + ora_eval[stats_block & 1]);
+    }
+    int ora_sampling = 0;  // 0: no overrepresented-sequence analysis
+    int ora_eval[2] = {0, 0};
+    Options::HotSet ora_set[2];
+    std::vector<uint64_t> ora;
 
    private:
     int ism_;
@@ -105,6 +126,21 @@ struct Summary {
     std::vector<double> content_curves[6];    // A, T, C, G, N, GC
     int kmer_k = 0;                           // mKmerLen (0: none)
     const uint64_t* kmer = nullptr;           // mKmer: 4^k counts (points into the HostAcc)
+    int ora_sampling = 0, ora_eval = 0;       // mOverRepSampling (0: none), mEvaluatedSeqLen
+    // mOverReqSeqCount / mOverRepSeqDist in map order: the sequence, then its count and distribution
+    // (pointing into the HostAcc)
+    std::vector<std::pair<std::string, const uint64_t*>> ora;
+    // Stats::overRepPassed (src/stats.cpp:372-386)
+    bool ora_passed(const std::string& seq, uint64_t count) const {
+        const uint64_t v = (uint64_t)ora_sampling * count;
+        switch (seq.size()) {
+            case 10: return v > 500;
+            case 20: return v > 200;
+            case 40: return v > 100;
+            case 100: return v > 50;
+            default: return v > 20;
+        }
+    }
     Json json;
     int mean_length() const { return reads ? (int)(length_sum / reads) : 0; }
 };

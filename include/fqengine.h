@@ -558,6 +558,38 @@ int fq_engine_set_kstat(fq_engine* e, fq_kstat* h); /* NULL detaches; h must be 
 int fq_kstat_read(fq_kstat* h, uint64_t* host, size_t words); /* waits for the device, then copies */
 double fq_kstat_last_kernel_ms(const fq_kstat* h);
 
+/* ---- overrepresented sequences (--ora --ora_sample s) -------------------------------------------
+ * The counts and per-cycle distributions of the four Stats objects (Stats::statRead, reference
+ * src/stats.cpp:277-293).  A hot set is the caller's (Evaluator::computeOverRepSeq): set 1 serves
+ * the read-1 Stats with evalLen1, set 2 the read-2 Stats with evalLen2; a set is its sequences'
+ * bytes back to back, sequence i = seq[off[i], off[i + 1]) (n + 1 offsets), raw bytes compared as
+ * they are, all distinct; n = 0 (seq and off may be NULL) is a valid empty set.
+ * Every Stats samples the reads whose number in ITS stream is a multiple of `sampling`: for the pre
+ * Stats a read's index over all packs so far, for the post Stats the number of reads that reached
+ * it before.  The handle keeps these four running counts on the device and advances them in stream
+ * order, so a handle is fed by ONE engine's packs in input order (unlike the k-mer tables, two
+ * handles' results do not add up to one stream's).  A sampled read of length len is scanned for
+ * each step of {10, 20, 40, 100, min(150, evalLen - 2)}: window j < len - step equal to a hot
+ * sequence adds 1 to its count and to its distribution at cycles [j, min(j + step, evalLen)), and
+ * the scan goes on at j + step + 1.  The passes sit where the k-mer passes do (pre: the original
+ * reads, before the main kernels; post: what the records say reached the post-filter statRead, a
+ * merged read in post-R1), through every entry point; records and accumulators do not change.
+ * fq_ora_read: four blocks [pre-R1 | pre-R2 | post-R1 | post-R2], block of set s = n_s x (1 +
+ * evalLen_s) uint64: per sequence, in the caller's order, its count and then its distribution.
+ * fq_ora_create refuses (FQ_E_INVALID) sampling < 1, an evalLen < 3 (the reference throws there),
+ * a sequence above 65535 bytes and a set with a repeated member.  Rows of more than 4096 bytes
+ * fail the pack.  fq_ora_reset zeroes the blocks and the four running counts.
+ * fq_ora_last_kernel_ms: device-event time of the last pack's two passes, milliseconds. */
+typedef struct fq_ora fq_ora;
+int fq_ora_create(int device, int32_t sampling, int32_t eval_len1, int32_t eval_len2, const uint8_t* seq1,
+                  const uint32_t* off1, int32_t n1, const uint8_t* seq2, const uint32_t* off2, int32_t n2, fq_ora** out);
+int fq_ora_destroy(fq_ora* h);
+int fq_ora_reset(fq_ora* h);                  /* waits for the device */
+size_t fq_ora_words(const fq_ora* h);
+int fq_engine_set_ora(fq_engine* e, fq_ora* h); /* NULL detaches; h must be on the engine's device */
+int fq_ora_read(fq_ora* h, uint64_t* host, size_t words); /* waits for the device, then copies */
+double fq_ora_last_kernel_ms(const fq_ora* h);
+
 /* ---- device BGZF: output text compressed on the GPU ---------------------------------------------
  * A span of text in device memory is cut into members of FQ_BGZF_IN input bytes (the last one
  * shorter; no bytes, no member).  Each member is a complete BGZF member laid out as the host

@@ -62,6 +62,15 @@ int fqh_session_set_dup(fqh_session* s, const uint64_t* hist, const uint64_t* gc
  * [pre-R1 | pre-R2 | post-R1 | post-R2], before fqh_session_finish (several calls add up) */
 int fqh_session_kmer_params(fqh_session* s, int* enabled, int* k);
 int fqh_session_set_kmer(fqh_session* s, const uint64_t* tables);
+/* --ora (honoured with FQ_ORA=1 in the environment): whether the command line enables it, the
+ * sampling (0 when it does not) and the two evaluated read lengths; the hot sets the pre-pass chose
+ * (which 0: the read-1 Stats', 1: the read-2 Stats'; sequence i = seq[off[i], off[i + 1]), *n + 1
+ * offsets, valid until the session closes); the caller counts (fq_ora_* with those sets on the
+ * engine's device) and hands back the four blocks [pre-R1 | pre-R2 | post-R1 | post-R2] before
+ * fqh_session_finish (-1 unless `words` is what the sets and lengths make). */
+int fqh_session_ora_params(fqh_session* s, int* enabled, int* sampling, int* eval_len1, int* eval_len2);
+int fqh_session_ora_hot_set(fqh_session* s, int which, const uint8_t** seq, const uint32_t** off, int* n);
+int fqh_session_set_ora(fqh_session* s, const uint64_t* blocks, size_t words);
 /* adds an accumulator block (fq_engine_read_acc layout at max_cycles) */
 int fqh_session_add_acc(fqh_session* s, const uint64_t* acc, int max_cycles);
 /* closes the outputs, writes the JSON report file (-J) and returns its text (malloc'd, fqh_free) */
