@@ -681,15 +681,30 @@ __device__ inline bool adseq_search(const uint32_t* col, int c, bool rc, int st,
 
 
 // PolyX::trimPolyG (src/polyx.cpp:14-38) on the code columns, one pass over 16-position groups
-// of scan indices (scan index i = forward position e - i, e = the window's last base).  A group
-// is one field_window of the column: read 2's column is the reverse complement, so its scan order
-// is the column order and a forward G is a stored C; read 1's group is the forward window
-// reversed.  The scan changes state only at non-G bases (with maxMM >= 0 the allowance never
-// shrinks, so a G never breaks it); a group whose non-G count cannot exceed the allowance at its
-// first index is passed over with one popcount, otherwise its non-G bases are visited in order
-// with find-first-set.  allowed(i) = min(maxMM, max(1, (i+1)/per)); (i+1)/per = ((i+1)*inv) >> 16
-// with inv = ceil(65536/per) is exact for i+1 <= 161 and per <= 256 (inv = 0 for per > 256, where
-// the quotient is 0 anyway).  firstGpos, the lowest G position the scan saw, is the highest G scan
+// of scan indices (scan index i = forward position e - i, e = the window's last base).  The scan
+// changes state only at non-G bases (with maxMM >= 0 the allowance never shrinks, so a G never
+// breaks it): it breaks at the k-th non-G base, at scan index q, for the smallest k with
+// k > allowed(q), allowed(i) = min(maxMM, max(1, (i+1)/per)).
+// The column words as a stream in scan order.  Read 2's column is the reverse complement, so its scan
+// order is the column order and a forward G is a stored C: stream word j is column word
+// (kMaxLen-1-e)/16 + j.  Read 1 scans downwards: stream word j is column word e/16 - j bit-reversed
+// (the two bits of a field swap, which the fold of a field's bits into its non-G flag does not see).
+// Scan index 0 sits at field ~e & 15 of stream word 0 in both, so group g (scan indices
+// [16g, 16g+16)) is one v_alignbit of stream words g and g+1 by a shift that is the same for every
+// group of a lane: a further group costs one new code word and one new N word (requested one group
+// ahead, before the current group is decided) at an address one step from the last.  Read 1's word
+// index stops at 0 (a partial last group would reach word -1); read 2's runs at most to word
+// kChunks + 1 of a field (the next field, or the columns / Stats blocks behind, valid LDS).  Either way
+// such words hold only scan indices >= n, which `valid` drops.
+// The groups are walked in wave-uniform steps, so what depends on the group alone is scalar work: the
+// allowance at its first index, a0, and at its last, a1 ((i+1)/per = ((i+1)*inv) >> 16 with
+// inv = ceil(65536/per), exact while per * (kMaxLen+1) < 65536; otherwise inv = 0: a division).  Inside
+// a group the k-th non-G base of the read cannot break for k <= a0, always breaks for k > a1, and for
+// a0 < k <= a1 breaks where allowed(q) < k, i.e. at a group position below k*per - 1 - 16g: a
+// wave-uniform position mask per such k (a1 - a0 of them: the multiples of per inside the group).  So a
+// lane drops its a0 - (non-G bases before the group) lowest non-G bases (x &= x - 1 each), then
+// tests one lowest base per k against that k's mask, and the first base left after them breaks.  No
+// allowance is evaluated per base.  firstGpos, the lowest G position the scan saw, is the highest G scan
 // index below the break, tracked per group.  Returns the new window length; bases < 0: not recorded.
 __device__ inline int polyg_bits(const uint32_t* col, int c, bool rc, int st, int n, int maxMM, int inv, int per,
                                  int compareReq, int& bases) {
@@ -700,64 +715,53 @@ __device__ inline int polyg_bits(const uint32_t* col, int c, bool rc, int st, in
     if (maxMM < 0) {
         iend = 0;  // mismatch 0 > allowed at the very first base
     } else {
-        int cum = 0;  // non-G bases before the current group
         const uint32_t gx = rc ? 0x55555555u : 0xFFFFFFFFu;  // (G is code 3; read 2's column holds C)
-        // spaced non-G mask (N and lowercase included) of scan indices [16g, 16g + 16), in scan order
-        auto nong = [&](int g) -> uint32_t {
-            const int pos0 = rc ? kMaxLen - 1 - e + 16 * g : e - 16 * g - 15;
-            // (positions outside [st, e] are scan indices >= n, dropped by `valid`)
-            const uint32_t cw = field_window_masked(col, kFC, c, pos0), nw = field_window_masked(col, kFN, c, pos0);
+        const int sh = 2 * (~e & 15);
+        const int step = rc ? 64 : -64;
+        int wo = 64 * max(rc ? kChunks - 1 - (e >> 4) : e >> 4, 0) + c;  // (e = -1: an empty window)
+        // a stream word's non-G bits (N and lowercase included), two per field, not yet folded
+        auto sword = [&](uint32_t cw, uint32_t nw) -> uint32_t {
             const uint32_t t = (cw ^ gx) | nw;
-            uint32_t x = (t | (t >> 1)) & 0x55555555u;
-            if (!rc) x = __builtin_bitreverse32(x) >> 1;  // forward window -> scan order
-            return x;
+            return rc ? t : __builtin_bitreverse32(t);
         };
-        uint32_t xg = nong(0);  // group g's non-G mask (group 0 first; later groups loaded one ahead)
-        // Group 0 decides almost every read: while the allowance is 1 (scan indices < 2 per - 1) the
-        // scan breaks at the second non-G base; the loop below runs only for the reads it leaves open
-        // (a polyG tail, or per < 8).
-        if (maxMM >= 1) {
-            const uint32_t valid = posmask_v(n), x = xg & valid, x2 = x & (x - 1u);
-            const int s2 = (__ffs(x2) - 1) >> 1;
-            if (x2 && (maxMM == 1 || s2 + 1 < 2 * per)) {
-                iend = s2;
-                const uint32_t gm = ~x & valid & posmask_v(s2);  // G bases before the break
-                if (gm) lastG = (31 - __clz(gm)) >> 1;
-            }
-        }
-        int g = 0;
-        // A polyG tail (the reads the shortcut above leaves open): its all-G groups change nothing
-        // but firstGpos, so they are passed over at ~16 VALU a group (the loop below spends ~45)
-        if (iend == n) {
-            while (16 * (g + 1) < n && (xg & posmask_v(n - 16 * g)) == 0u) xg = nong(++g);
-            if (g > 0) lastG = 16 * g - 1;  // (scan indices below 16 g are all G)
-        }
-        for (; 16 * g < n && iend == n; ++g) {
-            const uint32_t valid = posmask_v(n - 16 * g);
-            uint32_t x = xg & valid;
-            // the next group's column words are requested before this group is decided (a G tail
-            // spans several groups, and each LDS round trip otherwise stalls the few lanes that
-            // scan -- and with them their wave); past the window they are masked off by `valid`
-            xg = nong(g + 1);
-            uint32_t gm = ~x & valid;  // G bases of the group
-            const int a0 = allowed(16 * g + 1);  // allowance at the group start
-            if (cum + __popc(x) > a0) {
-                uint32_t m = x;
-                while (m) {
-                    const int t = (__ffs(m) - 1) >> 1;
-                    const int i = 16 * g + t;
-                    ++cum;
-                    if (cum > allowed(i + 1)) {
-                        iend = i;
-                        gm &= posmask(t);  // G bases before the break
-                        break;
+        uint32_t s0 = sword(col[kFC * 64 + wo], col[kFN * 64 + wo]);
+        wo = max(wo + step, c);
+        uint32_t cw = col[kFC * 64 + wo], nw = col[kFN * 64 + wo];  // stream word g + 1, as loaded
+        int cum = 0;  // non-G bases before the current group
+        bool open = n > 0;
+        for (int i0 = 0; __any(open); i0 += 16) {  // i0 = 16 g, wave-uniform
+            const int a0 = allowed(i0 + 1), a1 = allowed(i0 + 16);
+            if (open) {
+                const uint32_t s1 = sword(cw, nw);
+                const uint32_t al = __builtin_amdgcn_alignbit(s1, s0, sh);
+                const uint32_t xg = (al | (al >> 1)) & 0x55555555u;  // the group's spaced non-G mask
+                s0 = s1;
+                wo = max(wo + step, c);
+                cw = col[kFC * 64 + wo];
+                nw = col[kFN * 64 + wo];
+                const uint32_t valid = posmask_v(n - i0);
+                const uint32_t x = xg & valid;
+                uint32_t gm = ~xg & valid;  // G bases of the group
+                const int pc = __popc(x);
+                if (cum + pc > a0) {
+                    uint32_t m = x;
+                    for (int d = a0 - cum; d > 0; --d) m &= m - 1u;  // non-G bases 1 .. a0 of the read
+                    uint32_t brk = 0u;
+                    for (int k = a0 + 1; k <= a1; ++k) {  // (wave-uniform bounds)
+                        const uint32_t low = m & (0u - m);
+                        if (!brk && (low & posmask(k * per - 1 - i0))) brk = low;
+                        m &= m - 1u;
                     }
-                    m &= m - 1;
+                    if (!brk) brk = m & (0u - m);  // the (a1 + 1)-th breaks wherever it is
+                    if (brk) {
+                        iend = i0 + ((__ffs(brk) - 1) >> 1);
+                        gm &= brk - 1u;  // G bases before the break
+                    }
                 }
-            } else {
-                cum += __popc(x);
+                cum += pc;
+                if (gm) lastG = i0 + ((31 - __clz(gm)) >> 1);
+                open = iend == n && i0 + 16 < n;
             }
-            if (gm) lastG = 16 * g + ((31 - __clz(gm)) >> 1);
         }
     }
     bases = -1;
