@@ -118,6 +118,18 @@ class FqEgress(ctypes.Structure):  # fq_egress
     _fields_ = [("open", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class FqIndexFilter(ctypes.Structure):  # fq_index_filter
+    _fields_ = [("list", ctypes.c_void_p * 2), ("off", ctypes.c_void_p * 2), ("n", ctypes.c_int32 * 2),
+                ("threshold", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class FqCut(ctypes.Structure):  # fq_cut
+    _fields_ = [("bytes", ctypes.c_uint64 * 2), ("items", ctypes.c_uint32), ("passed", ctypes.c_uint32)]
+
+
+CUT_DTYPE = [("bytes", "<u8", (2,)), ("items", "<u4"), ("passed", "<u4")]
+
+
 class FqUmi(ctypes.Structure):  # fq_umi
     _fields_ = [("location", ctypes.c_int32), ("length", ctypes.c_int32), ("skip", ctypes.c_int32),
                 ("drop_comment", ctypes.c_uint8), ("not_trim", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 2)]
@@ -342,6 +354,14 @@ def load_engine(path=ENGINE_LIB):
     lib.fq_engine_set_umi.argtypes = [vp, ctypes.POINTER(FqUmi)]
     lib.fq_egress_bound_umi.argtypes = [i32, u64, u64, u64, ctypes.POINTER(FqUmi)]
     lib.fq_egress_bound_umi.restype = ctypes.c_size_t
+    lib.fq_engine_set_index_filter.argtypes = [vp, ctypes.POINTER(FqIndexFilter)]
+    lib.fq_engine_set_phred64.argtypes = [vp, ctypes.c_int]
+    lib.fq_cuts_bound.argtypes = [u64, u64]
+    lib.fq_cuts_bound.restype = ctypes.c_size_t
+    lib.fq_cuts_count.argtypes = [u64, u64, ctypes.c_uint32]
+    lib.fq_cuts_count.restype = ctypes.c_size_t
+    lib.fq_engine_set_cuts.argtypes = [vp, u64]
+    lib.fq_engine_next_cuts.argtypes = [vp, u64, vp, ctypes.c_uint32]
     cs = ctypes.c_size_t
     lib.fq_inflate_create.argtypes = [ctypes.c_int, cs, cs, cs, ctypes.POINTER(vp)]
     lib.fq_inflate_destroy.argtypes = [vp]
@@ -363,6 +383,8 @@ ENGINE_SYMBOLS = [
     "fq_deflate_bound", "fq_deflate_code_lengths", "fq_deflate_create", "fq_deflate_destroy", "fq_deflate_bgzf",
     "fq_engine_set_gz_out", "fq_egress_bound", "fq_engine_set_egress", "fq_engine_submit_text_routed", "fq_engine_raw_launch_routed",
     "fq_engine_set_umi", "fq_egress_bound_umi",
+    "fq_engine_set_index_filter", "fq_engine_set_phred64", "fq_cuts_bound", "fq_cuts_count", "fq_engine_set_cuts",
+    "fq_engine_next_cuts",
     "fq_inflate_create", "fq_inflate_destroy", "fq_inflate_members", "fq_inflate_bgzf", "fq_inflate_last_kernel_ms",
     "fq_kstat_create", "fq_kstat_destroy", "fq_kstat_reset", "fq_kstat_k", "fq_kstat_words", "fq_engine_set_kstat",
     "fq_kstat_read", "fq_kstat_last_kernel_ms",

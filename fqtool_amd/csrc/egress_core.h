@@ -206,9 +206,7 @@ struct Slice {
 // Read::firstIndex (src/read.h:106-123; host first_index) of the mate's name: the scan runs backwards
 // from len - 3, a '+' moves the end to the byte before it, the first ':' met ends the scan;
 // substr(i + 1, end - i) stops at the name's end
-FQ_EG_HD Slice first_index(const Mate& m) {
-    const char* nm = m.text + m.R.name_off;
-    const int n = (int)m.R.name_len;
+FQ_EG_HD Slice first_index(const char* nm, int n) {
     Slice s{nm, 0};
     if (n < 5) return s;
     int end = n;
@@ -224,6 +222,7 @@ FQ_EG_HD Slice first_index(const Mate& m) {
     }
     return s;
 }
+FQ_EG_HD Slice first_index(const Mate& m) { return first_index(m.text + m.R.name_off, (int)m.R.name_len); }
 
 // a pair's UMI tag: " OX:Z:" a ["-" b] and, when there is a quality part, " BZ:Z:" c ["-" d]; n: its
 // bytes (0: no tag, the names stay as they are)

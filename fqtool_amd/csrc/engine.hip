@@ -11,6 +11,7 @@
 #include <deque>
 #include <mutex>
 #include <unordered_map>
+#include <vector>
 #include <sys/mman.h>
 #include <string>
 
@@ -22,6 +23,7 @@ static bool prof_no_egress() {
 }
 
 #include "engine_internal.h"
+#include "ingest_core.h"
 
 // Tile list the fast kernel hands to the general kernel (one per concurrently running launch).
 struct Scratch {
@@ -82,6 +84,9 @@ struct Slot {
     bool copy_pending = false;
     char* copy_dst[2] = {nullptr, nullptr};
     size_t copy_cap[2] = {0, 0};
+    // pack cuts (fq_engine_next_cuts): the pack's table on the device, where it goes on the host
+    fq_cut* d_cuts = nullptr;
+    size_t cuts_cap = 0;
 };
 
 // A submitted pack, in submission order, until fq_engine_poll reports it.
@@ -135,6 +140,17 @@ struct fq_engine {
     // UMI description of the routed egress (fq_engine_set_umi)
     bool umi_on = false;
     fq_umi umi{};
+    // device ingest: the index filter's lists (fq_engine_set_index_filter), --phred64
+    bool idx_on = false;
+    uint32_t* d_idx = nullptr;
+    fq_index_lists idx{};
+    bool phred64 = false;
+    // pack cuts (fq_engine_set_cuts), and the table armed for the next pack (fq_engine_next_cuts)
+    uint64_t cut_every = 0;
+    bool cut_armed = false;
+    uint64_t cut_first = 0;
+    fq_cut* cut_host = nullptr;
+    uint32_t cut_cap = 0;
     uint64_t calls = 0;       // order of process / process_device packs for the table
     std::string last_error;
 };
@@ -217,6 +233,7 @@ static void free_slot(Slot& s) {
     if (s.d_rows) (void)hipFree(s.d_rows);
     if (s.d_lens) (void)hipFree(s.d_lens);
     if (s.d_flags) (void)hipFree(s.d_flags);
+    if (s.d_cuts) (void)hipFree(s.d_cuts);
     if (s.d_res) (void)hipFree(s.d_res);
     for (int m = 0; m < 2; ++m) {
         if (s.d_text[m]) (void)hipFree(s.d_text[m]);
@@ -354,6 +371,7 @@ int fq_engine_destroy(fq_engine* e) {
     if (e->own_acc) (void)hipFree(e->own_acc);
     if (e->xfix) (void)hipFree(e->xfix);
     if (e->err) (void)hipFree(e->err);
+    if (e->d_idx) (void)hipFree(e->d_idx);
     for (Slot& s : e->slots) free_slot(s);
     free_scratch(e->scratch);
     fq_deflate_scratch_free(e->gz);
@@ -631,6 +649,140 @@ static int ensure_text(fq_engine* e, Slot& s, const fq_text_batch* tb) {
     return FQ_OK;
 }
 
+// ---- device ingest and pack cuts (ingest.hip) -------------------------------------------------
+
+// the setters' call-time rule: nothing pending or enqueued, not inside a raw stream
+static int idle_for(fq_engine* e, const char* what) {
+    if (!e->pending.empty() || !e->raw_queued.empty()) return fail(e, FQ_E_INVALID, std::string(what) + " with packs in flight");
+    if (e->raw) return fail(e, FQ_E_INVALID, std::string(what) + " inside a raw stream");
+    return FQ_OK;
+}
+
+int fq_engine_set_index_filter(fq_engine* e, const fq_index_filter* f) {
+    if (!e) return FQ_E_INVALID;
+    const int rc = idle_for(e, "fq_engine_set_index_filter");
+    if (rc != FQ_OK) return rc;
+    std::vector<uint32_t> blob;
+    fq_index_lists L{};
+    if (f) {
+        if (f->threshold < 0 || f->reserved) return fail(e, FQ_E_INVALID, "fq_engine_set_index_filter: threshold must be >= 0, reserved 0");
+        uint64_t len[2] = {0, 0};
+        for (int m = 0; m < 2; ++m) {
+            const int32_t n = f->n[m];
+            if (n < 0 || (n > 0 && (!f->off[m] || f->off[m][0] != 0)))
+                return fail(e, FQ_E_INVALID, "fq_engine_set_index_filter: a list needs n >= 0 and n + 1 offsets from 0");
+            for (int32_t i = 0; i < n; ++i)
+                if (f->off[m][i + 1] < f->off[m][i] || f->off[m][i + 1] - f->off[m][i] > 65535u)
+                    return fail(e, FQ_E_INVALID, "fq_engine_set_index_filter: offsets must not decrease, entries hold at most 65535 bytes");
+            len[m] = n ? f->off[m][n] : 0;
+            if (len[m] && !f->list[m]) return fail(e, FQ_E_INVALID, "fq_engine_set_index_filter: missing list bytes");
+        }
+        const uint64_t head = 4ull * ((uint64_t)f->n[0] + (uint64_t)f->n[1] + 2), total = head + len[0] + len[1];
+        if (total >= (1ull << 31)) return fail(e, FQ_E_INVALID, "fq_engine_set_index_filter: the lists exceed 2 GiB");
+        blob.assign((size_t)((total + 3) / 4), 0u);
+        uint32_t* o = blob.data();
+        for (int m = 0; m < 2; ++m) {
+            for (int32_t i = 0; i <= f->n[m]; ++i) o[i] = f->n[m] ? f->off[m][i] : 0u;
+            o += f->n[m] + 1;
+        }
+        uint8_t* b = reinterpret_cast<uint8_t*>(o);
+        if (len[0]) std::memcpy(b, f->list[0], (size_t)len[0]);
+        if (len[1]) std::memcpy(b + len[0], f->list[1], (size_t)len[1]);
+        L.blob_bytes = (uint32_t)total;
+        L.n1 = (uint32_t)f->n[0], L.n2 = (uint32_t)f->n[1];
+        L.len1 = (uint32_t)len[0];
+        L.threshold = f->threshold;
+    }
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (e->d_idx) (void)hipFree(e->d_idx);  // (nothing is in flight: no kernel reads the old lists)
+    e->d_idx = nullptr;
+    e->idx_on = false;
+    e->idx = fq_index_lists{};
+    if (f) {
+        HIP_TRY(e, hipMalloc(&e->d_idx, blob.size() * sizeof(uint32_t)));
+        HIP_TRY(e, hipMemcpy(e->d_idx, blob.data(), blob.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        L.blob = e->d_idx;
+        e->idx = L;
+        e->idx_on = true;
+    }
+    return FQ_OK;
+}
+
+int fq_engine_set_phred64(fq_engine* e, int on) {
+    if (!e) return FQ_E_INVALID;
+    const int rc = idle_for(e, "fq_engine_set_phred64");
+    if (rc != FQ_OK) return rc;
+    if (on != 0 && on != 1) return fail(e, FQ_E_INVALID, "fq_engine_set_phred64: on must be 0 or 1");
+    e->phred64 = on != 0;
+    return FQ_OK;
+}
+
+size_t fq_cuts_bound(uint64_t every, uint64_t n) { return every ? (size_t)(n / every + 2) : 0; }
+size_t fq_cuts_count(uint64_t every, uint64_t first_item, uint32_t n) {
+    return every ? (size_t)fqingest::cut_count(every, first_item, n) : 0;
+}
+
+int fq_engine_set_cuts(fq_engine* e, uint64_t every) {
+    if (!e) return FQ_E_INVALID;
+    const int rc = idle_for(e, "fq_engine_set_cuts");
+    if (rc != FQ_OK) return rc;
+    if (every && e->p.paired && e->p.merge_enabled) return fail(e, FQ_E_INVALID, "fq_engine_set_cuts: the merged stream (-m) takes no cuts");
+    if (every && e->gz_level) return fail(e, FQ_E_INVALID, "fq_engine_set_cuts: no cuts while device BGZF output is on");
+    e->cut_every = every;
+    e->cut_armed = false;
+    return FQ_OK;
+}
+
+int fq_engine_next_cuts(fq_engine* e, uint64_t first_item, fq_cut* cuts, uint32_t cap) {
+    if (!e) return FQ_E_INVALID;
+    if (!e->cut_every) return fail(e, FQ_E_INVALID, "fq_engine_next_cuts without fq_engine_set_cuts");
+    if (!cuts || !cap) return fail(e, FQ_E_INVALID, "fq_engine_next_cuts: missing table");
+    e->cut_armed = true;
+    e->cut_first = first_item;
+    e->cut_host = cuts;
+    e->cut_cap = cap;
+    return FQ_OK;
+}
+
+// a plain pack of n records against the armed table, before anything is launched
+static int check_cuts(fq_engine* e, int n) {
+    if (e->cut_armed && (size_t)e->cut_cap < fq_cuts_bound(e->cut_every, (uint64_t)n))
+        return fail(e, FQ_E_INVALID, "pack cuts: the table is below fq_cuts_bound");
+    return FQ_OK;
+}
+
+// the ingest kernels of a text / raw pack whose text and records are in the slot, in front of its
+// tile kernels: the index filter's flags (which the device batch then carries), --phred64
+static int launch_ingest(fq_engine* e, Slot& s, int n, int stride, fq_batch& db) {
+    const bool pe = e->p.paired;
+    if (e->idx_on) {
+        HIP_TRY(e, fq_launch_index_flags(e->idx, s.d_text[0], s.d_trec[0], pe ? s.d_text[1] : nullptr, pe ? s.d_trec[1] : nullptr,
+                                         n, s.d_flags, e->stream));
+        db.flags = s.d_flags;
+    }
+    if (e->phred64)
+        for (int m = 0; m < (pe ? 2 : 1); ++m) HIP_TRY(e, fq_launch_phred64(s.d_text[m], s.d_trec[m], n, stride, e->stream));
+    return FQ_OK;
+}
+
+// the armed cut table of the pack launch_text_out has just sized, into the slot's device table
+// (*pieces entries, which the caller copies to e->cut_host behind the kernels)
+static int launch_cuts(fq_engine* e, Slot& s, int n, uint32_t* pieces) {
+    *pieces = (uint32_t)fq_cuts_count(e->cut_every, e->cut_first, (uint32_t)n);
+    if ((size_t)*pieces > s.cuts_cap) {
+        if (s.d_cuts) (void)hipFree(s.d_cuts);
+        s.d_cuts = nullptr;
+        s.cuts_cap = 0;
+        const size_t cap = (size_t)*pieces + (size_t)*pieces / 8 + 1;
+        HIP_TRY(e, hipMalloc(&s.d_cuts, cap * sizeof(fq_cut)));
+        s.cuts_cap = cap;
+    }
+    const bool pe = e->p.paired;
+    HIP_TRY(e, fq_launch_cuts(s.d_tsize[0], s.d_toff[0], pe ? s.d_tsize[1] : nullptr, pe ? s.d_toff[1] : nullptr, n, e->cut_every,
+                              e->cut_first, *pieces, s.d_cuts, e->stream));
+    return FQ_OK;
+}
+
 static int validate_host_batch(fq_engine* e, const fq_batch* hb) {
     const bool pe = e->p.paired;
     if (hb->n < 0 || hb->n > e->max_batch || hb->stride <= 0 || hb->stride > e->max_stride || (hb->stride & 15))
@@ -720,8 +872,12 @@ int fq_engine_submit_text(fq_engine* e, const fq_text_batch* tb, fq_read_result*
         if (tb->n > 0 && (!tb->text[m] || !tb->rec[m] || !out->text[m]))
             return fail(e, FQ_E_INVALID, "missing text pack arrays");
     const bool mrg = pe && e->p.merge_enabled;
+    int rc = check_cuts(e, tb->n);
+    if (rc != FQ_OK) return rc;
+    const bool cut = e->cut_armed;
     out->bytes[0] = out->bytes[1] = 0;
     if (tb->n == 0) {
+        e->cut_armed = false;  // (no records: no pieces)
         e->pending.push_back(Pending{seq_no, -1, true, 0});
         return FQ_OK;
     }
@@ -732,8 +888,7 @@ int fq_engine_submit_text(fq_engine* e, const fq_text_batch* tb, fq_read_result*
             k = (it->slot + 1) % kSlots;
             break;
         }
-    int rc = retire_slot(e, k);
-    if (rc != FQ_OK) return rc;
+    if ((rc = retire_slot(e, k)) != FQ_OK) return rc;
     Slot& s = e->slots[k];
     if ((rc = alloc_slot(e, s)) != FQ_OK) return rc;
     if ((rc = ensure_text(e, s, tb)) != FQ_OK) return rc;
@@ -755,7 +910,8 @@ int fq_engine_submit_text(fq_engine* e, const fq_text_batch* tb, fq_read_result*
     }
     HIP_TRY(e, hipEventRecord(s.ev_in, e->s_in));
     HIP_TRY(e, hipStreamWaitEvent(e->stream, s.ev_in, 0));
-    // planes from the text, the pack's kernels, then the output text
+    // the ingest kernels, planes from the text, the pack's kernels, then the output text
+    if ((rc = launch_ingest(e, s, tb->n, tb->stride, db)) != FQ_OK) return rc;
     for (int m = 0; m < (pe ? 2 : 1); ++m)
         HIP_TRY(e, fq_launch_text_tiles(s.d_text[m], s.d_trec[m], tb->n, tb->stride, const_cast<uint8_t*>(m ? db.seq2 : db.seq1),
                                         const_cast<uint8_t*>(m ? db.qual2 : db.qual1), const_cast<uint16_t*>(m ? db.len2 : db.len1),
@@ -763,6 +919,8 @@ int fq_engine_submit_text(fq_engine* e, const fq_text_batch* tb, fq_read_result*
     HIP_TRY(e, hipMemsetAsync(s.d_err, 0, sizeof(int), e->stream));
     if ((rc = launch(e, db, s.d_res, e->stream, s.scratch, false, false, seq_no, s.d_err)) != FQ_OK) return rc;
     if ((rc = launch_text_out(e, s, tb->n)) != FQ_OK) return rc;
+    uint32_t pieces = 0;
+    if (cut && (rc = launch_cuts(e, s, tb->n, &pieces)) != FQ_OK) return rc;
     size_t tback[2] = {0, 0};
     for (int m = 0; m < (mrg ? 1 : pe ? 2 : 1); ++m) {
         tback[m] = mrg ? merged_cap(tb->text_bytes[0], tb->text_bytes[1], (size_t)tb->n) : tb->text_bytes[m] + kTextSlack;
@@ -794,6 +952,10 @@ int fq_engine_submit_text(fq_engine* e, const fq_text_batch* tb, fq_read_result*
     HIP_TRY(e, hipStreamWaitEvent(e->s_out, s.ev_kern, 0));
     HIP_TRY(e, hipMemcpyAsync(results, s.d_res, nres * sizeof(fq_read_result), hipMemcpyDeviceToHost, e->s_out));
     HIP_TRY(e, hipMemcpyAsync(s.h_total, s.d_total, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->s_out));
+    if (cut) {  // (cuts and device BGZF exclude each other: the table always goes back here)
+        HIP_TRY(e, hipMemcpyAsync(e->cut_host, s.d_cuts, (size_t)pieces * sizeof(fq_cut), hipMemcpyDeviceToHost, e->s_out));
+        e->cut_armed = false;
+    }
     for (int m = 0; m < (mrg ? 1 : pe ? 2 : 1); ++m)
         HIP_TRY(e, hipMemcpyAsync(out->text[m], s.d_out[m], tback[m], hipMemcpyDeviceToHost, e->s_out));
     HIP_TRY(e, hipMemcpyAsync(s.h_err, s.d_err, sizeof(int), hipMemcpyDeviceToHost, e->s_out));
@@ -922,6 +1084,7 @@ int fq_engine_submit_text_routed(fq_engine* e, const fq_text_batch* tb, fq_read_
     if (!e->eg_on) return fail(e, FQ_E_INVALID, "routed text pack without fq_engine_set_egress");
     if (e->gz_level) return fail(e, FQ_E_INVALID, "routed text packs take no device BGZF output");
     if (e->raw) return fail(e, FQ_E_INVALID, "routed text pack inside a raw stream");
+    if (e->cut_armed) return fail(e, FQ_E_INVALID, "routed text packs take no pack cuts");
     if (tb->n < 0 || tb->n > e->max_batch || tb->stride <= 0 || tb->stride > e->max_stride || (tb->stride & 15))
         return fail(e, FQ_E_INVALID, "text pack exceeds the engine's max_batch/max_stride (or stride % 16 != 0)");
     if (umi_refused(e)) return fail(e, FQ_E_INVALID, "routed text packs take no UMI options");
@@ -972,6 +1135,7 @@ int fq_engine_submit_text_routed(fq_engine* e, const fq_text_batch* tb, fq_read_
     }
     HIP_TRY(e, hipEventRecord(s.ev_in, e->s_in));
     HIP_TRY(e, hipStreamWaitEvent(e->stream, s.ev_in, 0));
+    if ((rc = launch_ingest(e, s, tb->n, tb->stride, db)) != FQ_OK) return rc;
     for (int m = 0; m < mates; ++m)
         HIP_TRY(e, fq_launch_text_tiles(s.d_text[m], s.d_trec[m], tb->n, tb->stride, const_cast<uint8_t*>(m ? db.seq2 : db.seq1),
                                         const_cast<uint8_t*>(m ? db.qual2 : db.qual1), const_cast<uint16_t*>(m ? db.len2 : db.len1),
@@ -1197,18 +1361,25 @@ int fq_engine_raw_launch(fq_engine* e, fq_raw_result* r, fq_raw_out* out, uint64
     // (its two streams cannot hold what -c and --discard_unmerged write: fq_engine_raw_launch_routed)
     if (e->p.correction_enabled || (e->p.merge_enabled && e->p.discard_unmerged) || e->umi_on)
         return fail(e, FQ_E_INVALID, "raw streams take no -c, UMI or --discard_unmerged options");
+    if (e->phred64 && out->results) return fail(e, FQ_E_INVALID, "raw pack: records-only egress while --phred64 is on the device");
+    if (e->cut_armed && out->results) return fail(e, FQ_E_INVALID, "raw pack: records-only egress takes no pack cuts");
     HIP_TRY(e, hipSetDevice(e->device));
     const int k = e->raw_queued.front();
-    e->raw_queued.pop_front();
     Slot& s = e->slots[k];
     HIP_TRY(e, hipEventSynchronize(s.ev_idx));  // (returns at once after fq_engine_raw_wait)
     const bool pe = e->p.paired;
     const int mates = pe ? 2 : 1;
     raw_result_of(e, s, r);
     const int n = r->pairs;
+    // (a table below its bound is refused before the launch and leaves the window enqueued)
+    int rc = check_cuts(e, std::max(n, 0));
+    if (rc != FQ_OK) return rc;
+    const bool cut = e->cut_armed;
+    e->raw_queued.pop_front();
     out->text.bytes[0] = out->text.bytes[1] = 0;
     out->adapter_bytes[0] = out->adapter_bytes[1] = 0;
     if (n <= 0) {
+        e->cut_armed = false;  // (no records: no pieces)
         e->pending.push_back(Pending{seq_no, -1, true, 0});
         return FQ_OK;
     }
@@ -1226,13 +1397,15 @@ int fq_engine_raw_launch(fq_engine* e, fq_raw_result* r, fq_raw_out* out, uint64
     db.qual2 = pe ? s.d_rows + 3 * plane : nullptr;
     db.len2 = pe ? s.d_lens + e->max_batch : nullptr;
     HIP_TRY(e, hipStreamWaitEvent(e->stream, s.ev_idx, 0));
+    // (--phred64: only the taken records' quality lines; the carry, which the next window's index
+    // copies from this text, lies behind them and is converted with the window that takes it)
+    if ((rc = launch_ingest(e, s, n, db.stride, db)) != FQ_OK) return rc;
     for (int m = 0; m < mates; ++m)
         HIP_TRY(e, fq_launch_text_tiles(s.d_text[m], s.d_trec[m], n, db.stride, const_cast<uint8_t*>(m ? db.seq2 : db.seq1),
                                         const_cast<uint8_t*>(m ? db.qual2 : db.qual1), const_cast<uint16_t*>(m ? db.len2 : db.len1),
                                         e->stream));
     HIP_TRY(e, hipMemsetAsync(s.d_err, 0, sizeof(int), e->stream));
-    int rc = launch(e, db, s.d_res, e->stream, s.scratch, false, false, seq_no, s.d_err);
-    if (rc != FQ_OK) return rc;
+    if ((rc = launch(e, db, s.d_res, e->stream, s.scratch, false, false, seq_no, s.d_err)) != FQ_OK) return rc;
     HIP_TRY(e, hipMemsetAsync(s.d_total, 0, 4 * sizeof(unsigned long long), e->stream));
     if (recs_only) {  // the records and their line offsets back, no output text
         HIP_TRY(e, hipEventRecord(s.ev_kern, e->stream));
@@ -1258,6 +1431,13 @@ int fq_engine_raw_launch(fq_engine* e, fq_raw_result* r, fq_raw_out* out, uint64
     for (int m = 0; m < mates; ++m) back[m] = (size_t)r->text_bytes[m] + kTextSlack + 3 * (size_t)n;
     if (mrg) back[0] = merged_cap(r->text_bytes[0], r->text_bytes[1], (size_t)n) + 3 * (size_t)n;
     if ((rc = launch_text_out(e, s, n)) != FQ_OK) return rc;
+    // (the cut table before the adapter entries, which reuse the sizes' and offsets' buffers)
+    if (cut) {
+        uint32_t pieces = 0;
+        if ((rc = launch_cuts(e, s, n, &pieces)) != FQ_OK) return rc;
+        HIP_TRY(e, hipMemcpyAsync(e->cut_host, s.d_cuts, (size_t)pieces * sizeof(fq_cut), hipMemcpyDeviceToHost, e->stream));
+        e->cut_armed = false;
+    }
     // gz: each mate's text becomes BGZF members in place (d_total[m]: their bytes); the entries
     // follow them as they follow the text (members + entries <= the bound of text + entries)
     for (int m = 0; m < mates && e->gz_level; ++m) {
@@ -1291,6 +1471,7 @@ int fq_engine_raw_launch_routed(fq_engine* e, fq_raw_result* r, fq_raw_egress_ou
     if (!e->eg_on) return fail(e, FQ_E_INVALID, "routed raw pack without fq_engine_set_egress");
     if (e->gz_level) return fail(e, FQ_E_INVALID, "routed raw packs take no device BGZF output");
     if (e->raw_queued.empty()) return fail(e, FQ_E_INVALID, "fq_engine_raw_launch_routed without an enqueued window");
+    if (e->cut_armed) return fail(e, FQ_E_INVALID, "routed raw packs take no pack cuts");
     HIP_TRY(e, hipSetDevice(e->device));
     const int k = e->raw_queued.front();
     Slot& s = e->slots[k];
@@ -1331,13 +1512,14 @@ int fq_engine_raw_launch_routed(fq_engine* e, fq_raw_result* r, fq_raw_egress_ou
     db.qual2 = pe ? s.d_rows + 3 * plane : nullptr;
     db.len2 = pe ? s.d_lens + e->max_batch : nullptr;
     HIP_TRY(e, hipStreamWaitEvent(e->stream, s.ev_idx, 0));
+    int rc = launch_ingest(e, s, n, db.stride, db);
+    if (rc != FQ_OK) return rc;
     for (int m = 0; m < mates; ++m)
         HIP_TRY(e, fq_launch_text_tiles(s.d_text[m], s.d_trec[m], n, db.stride, const_cast<uint8_t*>(m ? db.seq2 : db.seq1),
                                         const_cast<uint8_t*>(m ? db.qual2 : db.qual1), const_cast<uint16_t*>(m ? db.len2 : db.len1),
                                         e->stream));
     HIP_TRY(e, hipMemsetAsync(s.d_err, 0, sizeof(int), e->stream));
-    int rc = launch(e, db, s.d_res, e->stream, s.scratch, false, false, seq_no, s.d_err);
-    if (rc != FQ_OK) return rc;
+    if ((rc = launch(e, db, s.d_res, e->stream, s.scratch, false, false, seq_no, s.d_err)) != FQ_OK) return rc;
     HIP_TRY(e, hipMemsetAsync(s.d_total, 0, 4 * sizeof(unsigned long long), e->stream));
     fq_egress_args a{};
     fq_egress_streams st{};
@@ -1391,6 +1573,7 @@ int fq_engine_set_gz_out(fq_engine* e, int32_t level) {
     if (level < 0 || level > 9) return fail(e, FQ_E_INVALID, "fq_engine_set_gz_out: level must be 0 (off) or 1..9");
     if (!e->pending.empty() || !e->raw_queued.empty())
         return fail(e, FQ_E_INVALID, "fq_engine_set_gz_out with packs in flight");
+    if (level && e->cut_every) return fail(e, FQ_E_INVALID, "fq_engine_set_gz_out: no device BGZF output while pack cuts are on");
     if ((level != 0) != (e->gz_level != 0)) {
         // the output buffers are sized for the stream's bound while gz is on: re-made on next use
         for (Slot& s : e->slots) {

@@ -93,6 +93,24 @@ hipError_t fq_launch_egress(const fq_egress_args& a, const fq_egress_streams& st
 hipError_t fq_launch_egress_adapters(const fq_egress_args& a, int m, uint32_t* d_size, uint32_t* d_off, void* d_temp,
                                      size_t temp_bytes, char* d_out, unsigned long long cap, unsigned long long* d_total,
                                      hipStream_t s);
+// Device ingest (ingest.hip).  The index filter's lists as the engine keeps them on the device: one
+// blob of whole 32-bit words, off1[n1 + 1] | off2[n2 + 1] | list 1's bytes | list 2's bytes
+struct fq_index_lists {
+    const uint32_t* blob;
+    uint32_t blob_bytes;
+    uint32_t n1, n2;
+    uint32_t len1;  // list 1's bytes (list 2's follow them)
+    int threshold;
+};
+// the pack's per-record FQ_BF_* flags (d_text2 / d_rec2 null: single end)
+hipError_t fq_launch_index_flags(const fq_index_lists& f, const char* d_text1, const fq_text_rec* d_rec1, const char* d_text2,
+                                 const fq_text_rec* d_rec2, int n, uint8_t* d_flags, hipStream_t s);
+// --phred64: the records' quality lines rewritten in place (stride: the pack's, >= every record's length)
+hipError_t fq_launch_phred64(char* d_text, const fq_text_rec* d_rec, int n, int stride, hipStream_t s);
+// the cut table of a pack's plain pair egress, from fq_launch_text_out's sizes and offsets of each
+// mate (d_size1 / d_off1 null: single end)
+hipError_t fq_launch_cuts(const uint32_t* d_size0, const uint32_t* d_off0, const uint32_t* d_size1, const uint32_t* d_off1, int n,
+                          uint64_t every, uint64_t first, uint32_t pieces, fq_cut* d_cuts, hipStream_t s);
 // Device BGZF (deflate.hip): scratch of the compressor, shared by the launches of one stream (they
 // run one after another): a token array per resident workgroup, a 64 KiB slot and a size per member
 struct fq_deflate_scratch {

@@ -1335,6 +1335,9 @@ void Pack::clear() {
     fix_arena.clear();
     flags.clear();
     use_flags = false;
+    cut = false;
+    first_item = 0;
+    n_cuts = 0;
 }
 
 fq_batch Pack::batch() const {

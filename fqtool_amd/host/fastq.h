@@ -323,6 +323,12 @@ struct Pack {
     bool zc = false;
     std::vector<iovec> segs[2];
     std::shared_ptr<void> hold;
+    // split outputs on the device route (fq_engine_next_cuts): the pack's first global record index
+    // and its cut table, n_cuts pieces once the pack is reported
+    bool cut = false;
+    uint64_t first_item = 0;
+    std::vector<fq_cut> cuts;
+    uint32_t n_cuts = 0;
 
     // -c: pairs whose bases the engine corrected read their seq/qual from a corrected copy
     // (fix[i] -> seq1 qual1 seq2 qual2 back to back; nullptr = the original text)

@@ -40,6 +40,14 @@
 // UMI (-u) on the routed egress: without these calls UMI runs keep the host packs
 #pragma weak fq_engine_set_umi
 #pragma weak fq_egress_bound_umi
+// The device ingest (index filter, --phred64) and the pack cuts of split outputs likewise: without
+// these calls such runs keep the host packs
+#pragma weak fq_engine_set_index_filter
+#pragma weak fq_engine_set_phred64
+#pragma weak fq_engine_set_cuts
+#pragma weak fq_engine_next_cuts
+#pragma weak fq_cuts_bound
+#pragma weak fq_cuts_count
 // The k-mer statistics (--kmer --kmer_length) are bound weakly too; without them such a run fails
 // with a message instead of leaving the KmerCount sections out.
 #pragma weak fq_kstat_create
@@ -874,6 +882,29 @@ class SplitSink {
             passed_ += passed(pk, res, cuts[j], cuts[j + 1]);
         }
     }
+    // a text pack's engine-written output: its two texts and the pieces the engine cut them into at
+    // the reference's pack boundaries (fq_engine_next_cuts with every = --max_item_in_pack)
+    void write_text(const char* t1, const char* t2, const fq_cut* cuts, uint32_t n_cuts, uint64_t first) {
+        const uint64_t P = std::max<uint64_t>(1, o_.max_reads_in_pack);
+        uint64_t at = first;
+        size_t o1 = 0, o2 = 0;
+        for (uint32_t j = 0; j < n_cuts; ++j) {
+            const fq_cut& c = cuts[j];
+            const uint64_t ref = at / P;
+            if (!have_ref_ || ref != ref_) {
+                finish_ref();
+                start_ref(ref);
+            }
+            Worker& w = th_[(size_t)t_];
+            if (w.w1) w.w1->write(std::vector<std::string>{std::string(t1 + o1, (size_t)c.bytes[0])}, pool_);
+            if (w.w2) w.w2->write(std::vector<std::string>{std::string(t2 + o2, (size_t)c.bytes[1])}, pool_);
+            o1 += (size_t)c.bytes[0];
+            o2 += (size_t)c.bytes[1];
+            count_ += c.items;
+            passed_ += c.passed;
+            at += c.items;
+        }
+    }
     void close() {
         finish_ref();
         for (int t = 0; t < T_; ++t) {
@@ -982,6 +1013,17 @@ bool Sink::plain_pair_outputs() const { return outs_ && !merge_ && outs_->plain_
 uint32_t Sink::egress_mask() const { return outs_ ? outs_->egress_mask() : 0u; }
 
 void Sink::consume_text(const Pack& pk, std::function<void()> done) {
+    if (split_) {  // (the split writers are synchronous)
+        if (!pk.cut || pk.first_item != pairs_) throw std::runtime_error("split output: a text pack without its cut table");
+        uint64_t items = 0, b1 = 0, b2 = 0;
+        for (uint32_t j = 0; j < pk.n_cuts; ++j) items += pk.cuts[j].items, b1 += pk.cuts[j].bytes[0], b2 += pk.cuts[j].bytes[1];
+        if (items != (uint64_t)pk.n || b1 != pk.tout.bytes[0] || b2 != pk.tout.bytes[1])
+            throw std::runtime_error("split output: the cut table disagrees with the pack's output");
+        split_->write_text(pk.out_text[0].data(), pk.out_text[1].data(), pk.cuts.data(), pk.n_cuts, pairs_);
+        pairs_ += (uint64_t)pk.n;
+        done();
+        return;
+    }
     pairs_ += (uint64_t)pk.n;
     if (pk.routed) outs_->write_routed(pk.eout, std::move(done));
     else if (pk.zc) outs_->write_text_segs(pk.segs[0], pk.segs[1], std::move(done));
@@ -1448,6 +1490,9 @@ struct Lane {
     uint32_t eg_open = 0;   // ... those writers, as FQ_EG_* bits
     bool umi_on = false;    // -u on the routed egress: the engine tags the names (fq_engine_set_umi)
     fq_umi umi{};
+    bool idx_dev = false;     // the index filter on the device (fq_engine_set_index_filter with the run's lists)
+    bool phred64_dev = false; // --phred64 on the device (fq_engine_set_phred64): the readers do not convert
+    uint64_t cut_every = 0;   // -s / -S on the device route: packs are cut every --max_item_in_pack records
     // a routed stream's buffer capacity for a pack.  (The engine refuses a UMI-tagged stream whose bound
     // passes 2^32 - 1, its cursors being 32-bit; this is not checked here before a window is sized: at
     // the index locations FAILED's bound is up to three times both mates' text, so windows of 48 MiB
@@ -1508,6 +1553,29 @@ struct Lane {
             if (umi_on && fq_engine_set_umi(e, &umi) != FQ_OK)
                 throw std::runtime_error(std::string("fq_engine_set_umi: ") + fq_engine_last_error(e));
         }
+        if (idx_dev) {  // the lists' lines as read (Options::index_list), bytes back to back
+            std::string bytes[2];
+            std::vector<uint32_t> off[2];
+            const std::vector<std::string>* lists[2] = {&o.blacklist1, &o.blacklist2};
+            fq_index_filter f{};
+            for (int m = 0; m < 2; ++m) {
+                off[m].push_back(0);
+                for (const std::string& x : *lists[m]) {
+                    bytes[m] += x;
+                    off[m].push_back((uint32_t)bytes[m].size());
+                }
+                f.list[m] = reinterpret_cast<const uint8_t*>(bytes[m].data());
+                f.off[m] = off[m].data();
+                f.n[m] = (int32_t)lists[m]->size();
+            }
+            f.threshold = o.index_threshold;
+            if (fq_engine_set_index_filter(e, &f) != FQ_OK)
+                throw std::runtime_error(std::string("fq_engine_set_index_filter: ") + fq_engine_last_error(e));
+        }
+        if (phred64_dev && fq_engine_set_phred64(e, 1) != FQ_OK)
+            throw std::runtime_error(std::string("fq_engine_set_phred64: ") + fq_engine_last_error(e));
+        if (cut_every && fq_engine_set_cuts(e, cut_every) != FQ_OK)
+            throw std::runtime_error(std::string("fq_engine_set_cuts: ") + fq_engine_last_error(e));
         max_cycles = cycles;
         max_batch = batch;
         max_stride = stride;
@@ -1544,6 +1612,16 @@ struct Lane {
         return true;
     }
 
+    // split outputs: the table of the pack about to be submitted or launched, which starts at global
+    // record `first` and holds at most n records
+    void arm_cuts(Pack& pk, uint64_t first, uint64_t n) {
+        pk.cut = true;
+        pk.first_item = first;
+        pk.cuts.resize(fq_cuts_bound(cut_every, n));
+        if (fq_engine_next_cuts(e, first, pk.cuts.data(), (uint32_t)pk.cuts.size()) != FQ_OK)
+            throw std::runtime_error(std::string("fq_engine_next_cuts: ") + fq_engine_last_error(e));
+    }
+
     void submit(Pack& pk, bool as_text) {
         const auto e0 = std::chrono::steady_clock::now();
         if (as_text) {
@@ -1578,8 +1656,10 @@ struct Lane {
                     }
                 pk.gz_members = true;
             }
+            if (cut_every) arm_cuts(pk, pk.first_item, (uint64_t)pk.n);
             if (fq_engine_submit_text(e, &tb, pk.results(), &pk.tout, pk.seq_no) != FQ_OK)
                 throw std::runtime_error(std::string("fq_engine_submit_text: ") + fq_engine_last_error(e));
+            if (cut_every) pk.n_cuts = (uint32_t)fq_cuts_count(cut_every, pk.first_item, (uint32_t)pk.n);
         } else {
             const fq_batch b = pk.batch();
             if (fq_engine_submit(e, &b, pk.results(), pk.seq_no) != FQ_OK)
@@ -1601,6 +1681,7 @@ struct Lane {
         bool done = false;
         uint64_t off[2] = {0, 0};
         uint64_t next_seq = 0;
+        uint64_t pairs = 0;  // the pairs (reads) the raw stream took: the next pack's first global index
     };
     struct Stage {  // one window's staging buffers (one per mate)
         Stage() : buf{ByteBuf(true), ByteBuf(true)} {}
@@ -1666,7 +1747,8 @@ struct Lane {
         // the formatter writes the output from the staging window, which then keeps the carry
         // capacity free in front of the window bytes (the device buffer's layout)
         const char* eg_env = std::getenv("FQ_RAW_EGRESS");
-        const bool recs = !merge && !gz_level && !routed && eg_env && std::string(eg_env) == "host";
+        // (not with --phred64 on the device: the host windows are never converted; nor with split outputs)
+        const bool recs = !merge && !gz_level && !routed && !phred64_dev && !cut_every && eg_env && std::string(eg_env) == "host";
         const uint64_t off0 = recs ? ccap : 0;
         const int raw_depth = 4;  // packs launched and not yet polled
         const size_t raw_ahead = 3;  // windows enqueued ahead of their launch (the copy-in queue)
@@ -1943,6 +2025,7 @@ struct Lane {
                         }
                         pk->gz_members = gz_level != 0;
                     }
+                    if (cut_every) arm_cuts(*pk, raw_pairs, (uint64_t)target);
                     fq_raw_result r{};
                     const auto e0 = std::chrono::steady_clock::now();
                     if (routed) {
@@ -1954,6 +2037,7 @@ struct Lane {
                     if (first_submit < 0) first_submit = since(t_start);
                     pk->n = r.pairs;
                     pk->max_cycles = max_cycles;
+                    if (cut_every) pk->n_cuts = (uint32_t)fq_cuts_count(cut_every, pk->first_item, (uint32_t)std::max(r.pairs, 0));
                     {
                         std::lock_guard<std::mutex> g(fb_m);
                         for (int m = 0; m < mates; ++m) {
@@ -2032,6 +2116,7 @@ struct Lane {
         for (int m = 0; m < mates; ++m)
             if (mp[m]) munmap(const_cast<char*>(mp[m]), (size_t)size[m]);
         rr.next_seq = seq;
+        rr.pairs = raw_pairs;
         if (gz_in) raw_end += " (gzip inputs inflated on " + std::to_string(gz_inflate_threads()) + " threads each)";
         return rr;
     }
@@ -2258,6 +2343,10 @@ struct Lane {
                 const auto p0 = std::chrono::steady_clock::now();
                 const bool as_text = text_mode && pack_text(*pk, &pool, o.merge);
                 if (!as_text) {
+                    // (--phred64 on the device: the reader left this pack's qualities as they are)
+                    if (phred64_dev)
+                        throw std::runtime_error("--phred64: a pack whose records do not fit a text pack (a line above 65535 bytes); "
+                                                 "FQ_TEXT_MODE=0 runs it through host packs");
                     pack_tiles(*pk, &pool);
                     prepare_pack(o, *pk, &pool);
                 }
@@ -2492,14 +2581,28 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
         // run goes as the run without -u that it is)
         const bool umi_tags = o.umi && o.umi_location != 0;
         const bool umi_ok = fq_engine_set_umi && fq_egress_bound_umi;
-        const bool eg_wanted = o.correction || !o.failed_out.empty() || !o.unpaired1.empty() || !o.unpaired2.empty() ||
-                               (o.merge && o.discard_unmerged) || umi_tags;
+        // Split outputs (-s / -S): the reference writes no failed / unpaired / merged output then
+        // (PairEndProcessor::process skips initOutput), so those options do not make a split run routed;
+        // the engine cuts each pack's two output texts at the reference's pack boundaries
+        // (fq_engine_set_cuts) and the SplitSink deals the pieces.  With -c, a UMI tag or -m a split run
+        // keeps the host packs.
+        const bool split = o.split();
+        const bool cuts_ok = fq_engine_set_cuts && fq_engine_next_cuts && fq_cuts_bound && fq_cuts_count;
+        const bool split_ok = !split || (cuts_ok && !o.correction && !umi_tags && !o.merge);
+        // The index filter and --phred64 run on the device (fq_engine_set_index_filter /
+        // fq_engine_set_phred64) on whichever route the other options select; --phred64 with -c keeps
+        // the host packs (the host re-applies the corrections to its own, unconverted, text).  An
+        // enabled filter with two empty lists drops nothing: nothing is attached.
+        const bool idx_lists = o.index_filter && (!o.blacklist1.empty() || !o.blacklist2.empty());
+        const bool ingest_ok = (!idx_lists || fq_engine_set_index_filter) && (!o.phred64 || (fq_engine_set_phred64 && !o.correction));
+        const bool eg_wanted = !split && (o.correction || !o.failed_out.empty() || !o.unpaired1.empty() || !o.unpaired2.empty() ||
+                                          (o.merge && o.discard_unmerged) || umi_tags);
         const bool eg_side = !o.failed_out.empty() || !o.unpaired1.empty() || !o.unpaired2.empty();
         const bool eg_unpaired_ok = o.unpaired2.empty() || (!o.unpaired1.empty() && o.unpaired1 != o.unpaired2);
         const bool eg_ok = fq_engine_set_egress && fq_egress_bound && fq_engine_submit_text_routed && eg_unpaired_ok &&
                            !(o.merge && eg_side) && (!(o.merge && o.discard_unmerged) || (!o.out1.empty() && !o.out2.empty()));
         const bool text_mode = !(tm_env && std::string(tm_env) == "0") && (!eg_wanted || eg_ok) && (!umi_tags || umi_ok) &&
-                               !o.index_filter && !o.split() && !o.phred64 &&
+                               split_ok && ingest_ok &&
                                (o.merge ? paired && !o.merge_out.empty()
                                         : !o.out1.empty() && (!paired || !o.out2.empty()));
         // (the records-only egress and device BGZF stay with the plain pair / merged outputs)
@@ -2539,7 +2642,7 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
         // the call, keep the host's compression
         const char* gzd_env = std::getenv("FQ_GZ_DEVICE");
         const bool gz_device = gzd_env && std::string(gzd_env) == "1" && fq_engine_set_gz_out && fq_deflate_bound &&
-                               text_mode && !routed && o.compression >= 1 && o.compression <= 9 &&
+                               text_mode && !routed && !split && o.compression >= 1 && o.compression <= 9 &&
                                (o.merge ? ends_with_gz(o.merge_out) : ends_with_gz(o.out1) && (!paired || ends_with_gz(o.out2)));
         for (int g = 0; g < G; ++g) {
             lanes.emplace_back(new Lane(devices[(size_t)g], depth));
@@ -2553,6 +2656,9 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
                 lanes.back()->umi = fq_umi{o.umi_location, o.umi_length, o.umi_skip, (uint8_t)o.umi_drop_comment,
                                            (uint8_t)o.umi_not_trim, {0, 0}};
             }
+            lanes.back()->idx_dev = text_mode && idx_lists;
+            lanes.back()->phred64_dev = text_mode && o.phred64;
+            lanes.back()->cut_every = text_mode && split ? std::max<uint64_t>(1, o.max_reads_in_pack) : 0;
             lanes.back()->make(o, cyc0, (int)pack_n, stride0);
         }
         const double engines_ready_s = since(t0);
@@ -2570,13 +2676,17 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
         };
         // (owned here, not by the reader thread: packs in flight point into its file mappings)
         // (BGZF inputs may inflate on the run's first device: FQ_GZ_IN_DEVICE=1)
-        PackReader pr(o.in1, o.in2, o.interleaved, o.phred64, 1 << 20, devices[0]);
+        // (--phred64 on the device routes: the engine converts its copy of the text, the reader's pages
+        // stay read-only and are copied straight from the mapping)
+        PackReader pr(o.in1, o.in2, o.interleaved, o.phred64 && !text_mode, 1 << 20, devices[0]);
         pr.defer_tiles = true;  // the dispatchers fill the planes while the reader parses on
         // GPU-side record indexing (fq_engine_raw_*) for plain files on one engine: the engine's
         // dispatcher drives the raw stream first; the host reader takes over only where it stops
         // (single-stream gzip inputs on one engine too: their streams come from the parallel
         // inflater -- RawMulti reads windows with pread, plain files only)
-        const bool raw_mode = text_mode && raw_ok && !o.interleaved && !(raw_env && std::string(raw_env) == "0") &&
+        // (split runs on several engines: text packs, whose first global record index the reader knows;
+        // RawMulti's engines learn a window's pairs only at its launch turn)
+        const bool raw_mode = text_mode && raw_ok && !(split && G > 1) && !o.interleaved && !(raw_env && std::string(raw_env) == "0") &&
                               ((!ends_with_gz(o.in1) && (!paired || !ends_with_gz(o.in2)) && pr.mapped()) ||
                                (gz_both && G == 1 && pr.parallel_gz()));
         std::promise<Lane::RawResume> raw_p;
@@ -2650,8 +2760,10 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
         }
         std::thread reader([&] {
             try {
+                uint64_t items_read = 0;
                 if (raw_mode) {  // wait for the raw stream's end; resume where it stopped
                     const Lane::RawResume rr = raw_f.get();
+                    items_read = rr.pairs;
                     if (rr.done) {
                         for (auto& l : lanes) l->in.close();
                         return;
@@ -2664,6 +2776,8 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
                     if (!spare.pop_recent(pk)) break;
                     spare_wait_s += since(w0);
                     if (!pr.next(*pk, pack_n, &pool)) break;
+                    pk->first_item = items_read;  // (split outputs: where the pack's cuts count from)
+                    items_read += (uint64_t)pk->n;
                     Lane& l = *lanes[(size_t)(pk->seq_no % (uint64_t)G)];
                     if (!l.in.push(std::move(pk))) break;
                 }
@@ -2701,7 +2815,7 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
             });
         }
         AdapterCounts ac;
-        uint64_t reads = 0, recs_packs = 0, zc_packs = 0;
+        uint64_t reads = 0, recs_packs = 0, zc_packs = 0, cut_pieces = 0;
         double format_s = 0;
         std::thread formatter([&] {
             try {
@@ -2740,6 +2854,7 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
                         }
                         format_s += since(f0);
                         reads += (uint64_t)pk->n * (paired ? 2 : 1);
+                        cut_pieces += pk->cut ? pk->n_cuts : 0;
                         // the writers recycle the pack once its output text is written
                         Pack* raw = pk.release();
                         outs.consume_text(*raw, [raw, &spare] { spare.push(std::unique_ptr<Pack>(raw)); });
@@ -2838,6 +2953,13 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
             for (auto& l : lanes) t += (*l).*f;
             return t;
         };
+        // what the device routes carried besides (tests key on these)
+        const std::string ingest_note = !text_mode ? std::string()
+                                                   : std::string(o.index_filter ? (idx_lists ? "; index filter on the device"
+                                                                                             : "; index filter on the device (empty lists)")
+                                                                                : "") +
+                                                         (o.phred64 ? "; phred64 on the device" : "") +
+                                                         (split ? "; " + std::to_string(cut_pieces) + " pack cuts" : std::string());
         log("fqtool-amd: " + std::to_string(reads) + " reads on " + std::to_string(G) + " engine(s)" +
             (raw_mode && rm ? " (raw stream on " + std::to_string(G) + " engines: host-cut pair windows, GPU record indexing, "
                               "ingest/egress: " + std::to_string(rm->pairs.load()) + " pairs in " + std::to_string(rm->packs.load()) +
@@ -2845,7 +2967,7 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
                               " s, reader waiting for a stage " + std::to_string(rm->stage_wait_s) + " s; engines waiting for their index " +
                               std::to_string(sum_lanes(&Lane::raw_idx_wait_s)) + " s, for their turn " +
                               std::to_string(sum_lanes(&Lane::raw_turn_wait_s)) + " s, for a pack " +
-                              std::to_string(sum_lanes(&Lane::raw_pack_wait_s)) + " s)"
+                              std::to_string(sum_lanes(&Lane::raw_pack_wait_s)) + " s" + ingest_note + ")"
              : raw_mode ? " (raw stream: GPU record indexing, ingest/egress: " + std::to_string(lanes[0]->raw_pairs) + " pairs in " +
                             std::to_string(lanes[0]->raw_packs) + " packs, ended: " + lanes[0]->raw_end + "; window reads " +
                             std::to_string(lanes[0]->raw_read_s) + " s, reader waiting for a stage " +
@@ -2854,10 +2976,11 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
                             " s, in enqueue " + std::to_string(lanes[0]->raw_enqueue_s) + " s" +
                             (recs_packs ? "; records-only egress: " + std::to_string(recs_packs) + " packs, " + std::to_string(zc_packs) +
                                               " as byte ranges of their windows" : std::string()) +
-                            (routed ? "; routed egress of " + std::to_string(__builtin_popcount(outs_mask)) + " output streams" : std::string()) + ")"
+                            (routed ? "; routed egress of " + std::to_string(__builtin_popcount(outs_mask)) + " output streams" : std::string()) +
+                            ingest_note + ")"
                       : routed    ? " (text packs: GPU ingest, routed egress of " + std::to_string(__builtin_popcount(outs_mask)) +
-                                        " output streams)"
-                      : text_mode ? " (text packs: GPU ingest/egress)" : "") + ", wall " +
+                                        " output streams" + ingest_note + ")"
+                      : text_mode ? " (text packs: GPU ingest/egress" + ingest_note + ")" : "") + ", wall " +
             std::to_string(since(t0)) + " s, engine submit " + std::to_string(submit_s) + " s, wait " + std::to_string(wait_s) + " s; pre-pass " +
             std::to_string(prepass_s) + " s, adapter detection (concurrent) " + std::to_string(detect_s) + " s, format " + std::to_string(format_s) + " s, parse " + std::to_string(parse_s) +
             " s, tiles " + std::to_string(tiles_s) + " s, reader waiting " + std::to_string(spare_wait_s) +

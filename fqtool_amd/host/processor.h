@@ -71,8 +71,9 @@ class Sink {
     Sink(const Options& o, Pool* pool);
     ~Sink();
     void consume(const Pack& pk, const fq_read_result* res);  // format + write one processed pack
-    // write a text pack's engine-assembled output (no split); `done` runs (on a writer thread) once
-    // the pack's text is written
+    // write a text pack's engine-assembled output; `done` runs (on a writer thread) once the pack's
+    // text is written.  With -s / -S the pack carries its cut table (Pack::cuts) and its pieces go
+    // to the split files
     void consume_text(const Pack& pk, std::function<void()> done);
     bool plain_pair_outputs() const;  // text packs may go out as byte ranges (Pack::zc)
     uint32_t egress_mask() const;     // the writers as FQ_EG_* bits (0 with -s / -S: no routed egress)

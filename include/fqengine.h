@@ -360,10 +360,11 @@ int fq_engine_pending(const fq_engine* e); /* packs submitted and not yet report
  * before the first space, when it merged and passes; otherwise each read that passes), written to
  * out->text[0] (which must then hold text_bytes[0] + text_bytes[1] + 24 * n + 16 bytes), and
  * out->bytes[1] is 0.  Only for options whose outputs are out1 (+ out2) or that merged stream: no
- * -c, UMI, index filter, phred64, split, failed or unpaired outputs, no --discard_unmerged; the
+ * -c, UMI, split, failed or unpaired outputs, no --discard_unmerged; the
  * routed egress below (fq_engine_set_egress, fq_engine_submit_text_routed) writes -c, failed,
- * unpaired and --discard_unmerged runs' streams, and the host routes everything else through
- * fq_engine_submit.  Records and text must stay valid until fq_engine_poll reports the pack; then
+ * unpaired and --discard_unmerged runs' streams, the index filter and --phred64 are attached with
+ * fq_engine_set_index_filter / fq_engine_set_phred64 (device ingest, below), and the host routes
+ * everything else (split outputs) through fq_engine_submit.  Records and text must stay valid until fq_engine_poll reports the pack; then
  * `results` holds the records as from fq_engine_submit and out->bytes[m] the bytes of out->text[m].
  * out->text[m] must hold at least the mate's text_bytes + 16 (a record's output is never longer
  * than its input text, except by the final line terminator that the input may lack). */
@@ -411,8 +412,8 @@ int fq_engine_submit_text(fq_engine* e, const fq_text_batch* tb, fq_read_result*
  * launched or not yet polled: a ninth enqueue waits for the oldest pack's copies); a window's
  * host bytes must stay valid until its pack is reported by fq_engine_poll.  Options as for text
  * packs (-m writes the merged stream into out->text.text[0], which must then hold both mates' window
- * and carry bytes + 28 * max_batch + 64; no -c, UMI, index filter, --discard_unmerged: those go
- * through fq_engine_raw_launch_routed below).
+ * and carry bytes + 28 * max_batch + 64; no -c, UMI, --discard_unmerged: those go
+ * through fq_engine_raw_launch_routed below; the index filter and --phred64 as for text packs).
  * The trimmed-adapter strings (FilterResult::addAdapterTrimmed, src/filterresult.cpp:138-157) come
  * back after the output text, at out->text.text[m] + out->text.bytes[m], adapter_bytes[m] bytes of
  * entries "u16 ad_len (little endian), u8 neg, then ad_len bytes of the read (neg 0) or u16
@@ -735,6 +736,75 @@ typedef struct fq_umi {
 } fq_umi;
 int fq_engine_set_umi(fq_engine* e, const fq_umi* u);
 size_t fq_egress_bound_umi(int32_t stream, uint64_t text_bytes1, uint64_t text_bytes2, uint64_t n, const fq_umi* u);
+
+/* ---- device ingest: the index filter and --phred64 on text packs and the raw stream ---------------
+ * Index filter (--enable_index_filter; Filter::filterByIndex, src/filter.cpp:191-232, which runs on
+ * the input names before the UMI step, src/peprocessor.cpp:283-290).  With a filter attached every
+ * text-pack and raw-stream entry point (fq_engine_submit_text, fq_engine_submit_text_routed,
+ * fq_engine_raw_launch, fq_engine_raw_launch_routed) runs one more kernel before the pack's main
+ * kernels: it writes the pack's per-record FQ_BF_* flags, which the device batch then carries as a
+ * host pack's fq_batch.flags would:
+ *     flags[i] = match(list 1, firstIndex(name1)) || (paired && match(list 2, firstIndex(name2)))
+ * firstIndex is Read::firstIndex (src/read.h:106-123) of the record's name line as it stands in the
+ * text.  match is Filter::match: an entry matches when its mismatches with the index over
+ * min(entry length, index length) bytes are <= threshold, so an empty index or an empty entry matches
+ * whenever the list has an entry at all, and an empty list never matches.  Single end uses list 1
+ * only.  A list is its entries' bytes back to back, entry i = list[m][off[m][i], off[m][i + 1])
+ * (n[m] + 1 offsets), raw bytes compared as they are; n[m] = 0 (list and off may be NULL) is the empty
+ * list.  The engine keeps a device copy, so the caller's arrays may go after the call.
+ * fq_engine_set_index_filter (only while no pack is pending or enqueued, and not inside a raw stream,
+ * else FQ_E_INVALID): NULL (the default) detaches the filter.  Refused (FQ_E_INVALID): a negative
+ * threshold or n, offsets that do not start at 0 or decrease, an entry above 65535 bytes, reserved
+ * not 0.  fq_engine_submit and fq_engine_process* keep taking the caller's fq_batch.flags.
+ * --phred64 (Read::convertPhred64To33, src/read.h:71-75: q = max(33, (signed char)q - 31), so bytes
+ * >= 128 become 33).  fq_engine_set_phred64 (the same call-time rules; on = 0 / 1) makes the same
+ * entry points rewrite the quality line of every record of the pack in the device copy of the text,
+ * in place, before the tile planes are built: planes, Stats, the output text, UMI BZ:Z: parts and
+ * adapter entries all read that copy.  On the raw stream only a window's taken records are
+ * converted: the carried bytes belong to records not yet taken (each is converted exactly once, in
+ * the window that takes it), and a caller that resumes with its own reader does so on the
+ * unconverted input.  The records-only egress (fq_raw_out.results) is refused while it is on: its
+ * caller formats from host windows that were never converted. */
+typedef struct fq_index_filter {
+    const uint8_t* list[2];  /* list 1 / list 2 (paired end), entries back to back */
+    const uint32_t* off[2];  /* n[m] + 1 offsets into list[m] */
+    int32_t n[2];
+    int32_t threshold;       /* --max_diff_for_match, >= 0 */
+    int32_t reserved;        /* 0 */
+} fq_index_filter;
+int fq_engine_set_index_filter(fq_engine* e, const fq_index_filter* f);
+int fq_engine_set_phred64(fq_engine* e, int on);
+
+/* ---- pack cuts: where the reference's packs end inside a text pack (split outputs, -s / -S) -------
+ * The reference closes and opens split files only between its own packs of --max_item_in_pack reads
+ * (ThreadConfig::markProcessed, src/threadconfig.cpp:88-137).  An engine with cuts on describes, for
+ * a pack whose first record has global index first_item (the records taken by all earlier packs of
+ * the input), the pieces the pack falls into when it is cut in front of every record whose global
+ * index is a multiple of `every`: fq_cuts_count(every, first_item, n) pieces, piece j holding the
+ * pack's records of global index [(first_item / every + j) * every, ... + every).  Per piece:
+ * bytes[m] = the output bytes of stream m (OUT1 / OUT2; single end: bytes[1] = 0) its records wrote,
+ * so the pieces' bytes[m] add up to out->bytes[m] and piece j's text starts where piece j - 1's
+ * ends; items = its records; passed = its records that were written (a pair both of whose reads
+ * pass, a passing read in single end).  A piece may be empty of passing records (bytes 0).
+ * fq_engine_set_cuts (only while no pack is pending or enqueued, and not inside a raw stream, else
+ * FQ_E_INVALID): every = 0 (the default) turns cuts off; refused with -m (the merged stream is not a
+ * split output) and while device BGZF is on (fq_engine_set_gz_out, which in turn is refused while
+ * cuts are on).  fq_engine_next_cuts arms the table for the next pack of fq_engine_submit_text or
+ * fq_engine_raw_launch only: `cuts` (host memory, cap entries) is filled when fq_engine_poll reports
+ * that pack, and must stay valid until then.  The pack's call refuses (FQ_E_INVALID, before anything
+ * is launched; a raw window stays enqueued, the table stays armed) cap < fq_cuts_bound(every, n), n
+ * being the pack's records, and the records-only egress; the routed calls refuse while a table is
+ * armed.  A pack submitted without fq_engine_next_cuts gets no table.  fq_cuts_bound and
+ * fq_cuts_count need no device. */
+typedef struct fq_cut {
+    uint64_t bytes[2];
+    uint32_t items;
+    uint32_t passed;
+} fq_cut;
+size_t fq_cuts_bound(uint64_t every, uint64_t n);                           /* n / every + 2 (0 for every = 0) */
+size_t fq_cuts_count(uint64_t every, uint64_t first_item, uint32_t n);      /* pieces of such a pack (0 for n = 0) */
+int fq_engine_set_cuts(fq_engine* e, uint64_t every);
+int fq_engine_next_cuts(fq_engine* e, uint64_t first_item, fq_cut* cuts, uint32_t cap);
 
 /* ---- device inflate: BGZF input members inflated on the GPU ---------------------------------------
  * The mirror of device BGZF.  Every BGZF member is an independent raw deflate stream (RFC 1951)
