@@ -169,6 +169,22 @@ __device__ __forceinline__ int xor32(int x) {
 }
 __device__ __forceinline__ uint32_t xor32(uint32_t x) { return (uint32_t)xor32((int)x); }
 
+// 16 bytes of a row chunk.  NT (global_load_dwordx4 ... nt): the row's only or last read by this
+// kernel -- the sequence rows at staging, the quality rows in the removed-mode Stats pass -- so the
+// line gives way in L2 to the quality lines still waiting for their second read.  With the record
+// stores (nt as well): C3 -1.4 % at 100 M pairs, -0.9 to -1.5 % at 20 M, C2 -4.5 %, fabric traffic
+// 100.2 -> 88.1 GB per 100 M pairs; the sequence loads alone stay inside the parent's spread
+// (profiles/r13_ab_stage_req.txt).
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+template <bool NT>
+__device__ __forceinline__ uint4 load16(const uint8_t* a) {
+    if constexpr (NT) {
+        const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(a));
+        return make_uint4(v.x, v.y, v.z, v.w);
+    }
+    return *reinterpret_cast<const uint4*>(a);
+}
+
 // A uniform value kept in a VGPR (opaque to the compiler, which would otherwise keep it in an SGPR or
 // rematerialise it there): on gfx950 a full-rate VALU op (and, xor, add, bitop3, ...) with an SGPR
 // operand issues at the half rate of the VOP3 ops (profiles/r04_micro_opcost2.txt).
@@ -1113,12 +1129,6 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
     constexpr int kWaves = LY::kWaves, kThreads = LY::kThreads;
     // the paired exact check where it fits the registers (FULL without -m spills with it)
     constexpr bool kOvx2 = LEAN || MERGE;
-    // Never set.  It guarded the merge variant's quality rows staged in LDS, a rejected experiment
-    // that no longer fits the LDS budget; its arms in staging's dword() and in qchunk() below are
-    // dead, but they shape those closures' captures, and without them the compiler orders the
-    // staging loads of most instantiations differently.  They go with the next change that
-    // re-times the kernel.
-    constexpr bool kQLds = false;
     uint32_t* col = lds + wave * LY::kWaveW;  // code / N columns: word field*64 + lane
     uint32_t* hist = lds + LY::kColsW;        // [pre1, pre2, post1, post2] x kHistW (post1 x2 with MERGE)
     unsigned long long* small = reinterpret_cast<unsigned long long*>(hist + LY::kHistRegW);
@@ -1219,7 +1229,6 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
         uint32_t* my_pre = hist + mate * kHistW;
         uint32_t* my_post = hist + (2 + (MERGE ? 2 : 1) * mate) * kHistW;  // post block, or the "removed" block
         const int r = lane_x & 15;  // stats rotation within a chunk
-        uint32_t* qrow = col + kCodeW + lane_x * (kMaxLen / 4 + 1);  // (kQLds: dead)
         const int idx = PAIRED ? t * 32 + pl : t * 64 + lane_x;
         bool valid = idx < b.n;  // (both cleared below for a pair handed to the general kernel)
         int L = valid ? (int)(mate ? b.len2[idx] : b.len1[idx]) : 0;
@@ -1235,10 +1244,9 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
         const uint8_t* S = (mate ? b.seq2 : b.seq1) + roff;
         const uint8_t* Q = (mate ? b.qual2 : b.qual1) + roff;
         // quality chunk F of this lane's row, re-read from the row (an L2 hit after staging)
-        auto qchunk = [&](int F) -> uint4 {
-            if (!kQLds) return *reinterpret_cast<const uint4*>(Q + cst * F);
-            return make_uint4(qrow[4 * F], qrow[4 * F + 1], qrow[4 * F + 2], qrow[4 * F + 3]);
-        };
+        auto qchunk = [&](int F) -> uint4 { return *reinterpret_cast<const uint4*>(Q + cst * F); };
+        // (the removed-mode Stats pass's: the row's last read)
+        auto qchunk_last = [&](int F) -> uint4 { return load16<true>(Q + cst * F); };
         // (merge: a merged read, at most len1 + len2 long, must fit max_cycles as well)
         const bool odd = L > kMaxLen || L > p.max_cycles || L > (nchunks << 4) ||
                          (MERGE && L + xor32(L) > p.max_cycles);
@@ -1267,15 +1275,15 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
         uint4 sb[kChunks], qb[kChunks];
 #pragma unroll
         for (int k = 0; k < kAhead && k < kChunks; ++k) {
-            sb[k] = *reinterpret_cast<const uint4*>(S + cst * min(k, lastc));
-            qb[k] = *reinterpret_cast<const uint4*>(Q + cst * min(k, lastc));
+            sb[k] = load16<true>(S + cst * min(k, lastc));
+            qb[k] = load16<false>(Q + cst * min(k, lastc));
         }
 #pragma unroll
         for (int k = 0; k < kChunks; ++k) {
             const uint4 s4 = sb[k], q4 = qb[k];
             if (k + kAhead < kChunks) {
-                sb[k + kAhead] = *reinterpret_cast<const uint4*>(S + cst * min(k + kAhead, lastc));
-                qb[k + kAhead] = *reinterpret_cast<const uint4*>(Q + cst * min(k + kAhead, lastc));
+                sb[k + kAhead] = load16<true>(S + cst * min(k + kAhead, lastc));
+                qb[k + kAhead] = load16<false>(Q + cst * min(k + kAhead, lastc));
             }
             // keep the loads where they are: left alone, the scheduler hoists them all to the top
             // of the tile and then waits for every one of them before chunk 0
@@ -1299,7 +1307,6 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                 constexpr bool kChunkMask = LEAN || MERGE;
                 auto dword = [&](int j, auto full_c) {
                     constexpr bool FULL = decltype(full_c)::value;
-                    if (kQLds) qrow[4 * k + j] = qw[j];
                     const uint32_t bm = FULL ? 0xFFFFFFFFu : kChunkMask ? pbm[j] : bytemask(Lk - 4 * j);
                     // read 2 (the column holds its reverse complement): the chunk's bytes reversed
                     // (dword 3 - j byte-swapped, one v_perm), so its codes come out in column order
@@ -1962,7 +1969,7 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
             constexpr int kSA = 2;
             uint4 qb[kSA + 1];
 #pragma unroll
-            for (int i = 0; i < kSA; ++i) qb[i] = qchunk(min(i, nchunks - 1));
+            for (int i = 0; i < kSA; ++i) qb[i] = qchunk_last(min(i, nchunks - 1));
             // this lane's column word of forward chunk F: cw0 + F * cstep (read 2's column is reversed)
             const uint32_t* cwp = col + lane_x + (rc ? (kChunks - 1) * 64 : 0);
             const int cstep = rc ? -64 : 64;
@@ -2014,7 +2021,7 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                     }
                     const uint32_t q0 = qb[F % (kSA + 1)].x, q1 = qb[F % (kSA + 1)].y, q2 = qb[F % (kSA + 1)].z,
                                    q3 = qb[F % (kSA + 1)].w;
-                    if (F + kSA < kChunks) qb[(F + kSA) % (kSA + 1)] = qchunk(min(F + kSA, nchunks - 1));
+                    if (F + kSA < kChunks) qb[(F + kSA) % (kSA + 1)] = qchunk_last(min(F + kSA, nchunks - 1));
                     // (chunks from nch on are zero-filled by staging: no clamp)
                     if (!kPf2 && F + 1 < kChunks) {
                         cwp += cstep;
@@ -2282,7 +2289,10 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                                        (uint32_t)rr.code | (uint32_t)rr.flags << 8 | (uint32_t)rr.ad_pos << 16,
                                        (uint32_t)rr.ad_len | (uint32_t)rr.m_len1 << 16,
                                        (uint32_t)rr.m_len2 | (uint32_t)rr.reserved << 16);
-            if (res) *reinterpret_cast<uint4*>(&res[PAIRED ? 2 * (size_t)idx + mate : (size_t)idx]) = w;
+            // (written once, read by no wave: nt, as the rows read once)
+            if (res)
+                __builtin_nontemporal_store(u32x4_t{w.x, w.y, w.z, w.w},
+                                            reinterpret_cast<u32x4_t*>(&res[PAIRED ? 2 * (size_t)idx + mate : (size_t)idx]));
         }
     }
     if (lane < hres[2 * wave + 1]) slow_tiles[hres[2 * wave] + lane] = kHole;  // the rest of the last reservation
