@@ -6,6 +6,8 @@
 // members into one contiguous stream, and writes its length.  The text's length is read on the
 // device (the engine knows only a bound of it when it enqueues the kernels), so the grids are
 // sized by that bound and workgroups beyond the real length leave at once.
+// fq_deflate_spans_kernel / fq_compact_spans_kernel do the same for up to six texts at once (a
+// routed pack's streams): one global member index runs over all of them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,33 +43,27 @@ __global__ __launch_bounds__(256) void fq_compact_kernel(const unsigned long lon
     const unsigned long long nmem = (n + FQ_BGZF_IN - 1) / FQ_BGZF_IN;
     if (nmem == 0 && blockIdx.x == 0 && tid == 0) *d_total = 0;
     for (unsigned long long m = blockIdx.x; m < nmem; m += gridDim.x) {
-        unsigned long long sum = 0;
-        for (unsigned long long i = tid; i < m; i += 256) sum += sizes[i];
-        part[tid] = sum;
-        __syncthreads();
-        for (uint32_t s = 128; s > 0; s >>= 1) {
-            if (tid < s) part[tid] += part[tid + s];
-            __syncthreads();
-        }
-        const unsigned long long off = part[0];
-        __syncthreads();
-        const uint32_t sz = sizes[m];
-        const uint8_t* src = slots + m * FQ_DEFL_SLOT;
-        if (sz <= FQ_DEFL_SLOT && off + sz <= dst_cap) {
-            // 4 bytes a thread once the destination is aligned (the slot is; the stream offset is not)
-            const uint32_t head = std::min<uint32_t>(sz, (uint32_t)((4 - ((uintptr_t)(dst + off) & 3)) & 3));
-            if (tid < head) dst[off + tid] = src[tid];
-            const uint32_t words = (sz - head) / 4;
-            uint32_t* d4 = (uint32_t*)(dst + off + head);
-            for (uint32_t i = tid; i < words; i += 256) {
-                const uint8_t* q = src + head + 4 * i;
-                d4[i] = (uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16 | (uint32_t)q[3] << 24;
-            }
-            const uint32_t done = head + 4 * words;
-            if (tid < sz - done) dst[off + done + tid] = src[done + tid];
-        }
-        if (m == nmem - 1 && tid == 0) *d_total = off + sz;
+        const unsigned long long end = fq_compact_member(part, slots, sizes, 0, m, dst, dst_cap);
+        if (m == nmem - 1 && tid == 0) *d_total = end;
     }
+}
+
+// ---- several spans by one launch (the routed egress's streams) -------------------------------------
+// The table goes to the kernels by value; every workgroup reads the length words and derives the same
+// layout, then takes every gridDim.x-th member of all spans (deflate_core.h has both walks).
+static_assert(FQ_DEFL_SPANS == FQ_EG_STREAMS && FQ_DEFL_MEMBER_IN == FQ_BGZF_IN, "deflate_core.h restates fqengine.h");
+
+__global__ __launch_bounds__(FQ_DEFL_THREADS) void fq_deflate_spans_kernel(fq_span_table t, unsigned long long members, int level,
+                                                                           uint32_t* tok, uint8_t* slots, uint32_t* sizes) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t fq_defl_lds[];
+    fq_deflate_spans_walk(fq_defl_lds, t, members, level, tok + (size_t)blockIdx.x * FQ_BGZF_IN, slots, sizes, blockIdx.x,
+                          gridDim.x);
+}
+
+__global__ __launch_bounds__(256) void fq_compact_spans_kernel(fq_span_table t, unsigned long long members, const uint8_t* slots,
+                                                               const uint32_t* sizes, unsigned long long* totals, int* err) {
+    __shared__ unsigned long long part[256];
+    fq_compact_spans_walk(part, t, members, slots, sizes, totals, err, blockIdx.x, gridDim.x);
 }
 
 static size_t members_of(size_t bytes) { return (bytes + FQ_BGZF_IN - 1) / FQ_BGZF_IN; }
@@ -85,12 +81,14 @@ hipError_t fq_deflate_scratch_ensure(fq_deflate_scratch& sc, size_t max_bytes, i
     if (members <= sc.members) return hipSuccess;
     hipError_t e = hipFuncSetAttribute((const void*)fq_deflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FQ_DL_TOTAL);
     if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute((const void*)fq_deflate_spans_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FQ_DL_TOTAL);
+    if (e != hipSuccess) return e;
     fq_deflate_scratch_free(sc);  // (hipFree waits for the device: no launch still uses the old buffers)
     const int grid = (int)std::min<size_t>(members, (size_t)2 * std::max(1, cus));
     if ((e = hipMalloc(&sc.tok, (size_t)grid * FQ_BGZF_IN * sizeof(uint32_t))) != hipSuccess) return e;
     if ((e = hipMalloc(&sc.slots, members * FQ_DEFL_SLOT)) != hipSuccess) return e;
     if ((e = hipMalloc(&sc.sizes, members * sizeof(uint32_t))) != hipSuccess) return e;
-    if ((e = hipMalloc(&sc.total, sizeof(unsigned long long))) != hipSuccess) return e;
+    if ((e = hipMalloc(&sc.total, FQ_EG_STREAMS * sizeof(unsigned long long))) != hipSuccess) return e;
     sc.members = members;
     sc.grid = grid;
     sc.cus = std::max(1, cus);
@@ -113,6 +111,33 @@ hipError_t fq_launch_deflate(const fq_deflate_scratch& sc, const void* d_text, c
     if ((e = hipGetLastError()) != hipSuccess) return e;
     // (d_total may be the word d_n points to: it is replaced only after both kernels have read it)
     return hipMemcpyAsync(d_total, sc.total, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s);
+}
+
+hipError_t fq_launch_deflate_spans(const fq_deflate_scratch& sc, const fq_deflate_span* spans, int level,
+                                   unsigned long long* d_totals, int* d_err, hipStream_t s) {
+    if (level < 1 || level > 9 || !sc.members) return hipErrorInvalidValue;
+    fq_span_table t{};
+    size_t bound = 0;  // members the capacities allow
+    for (int k = 0; k < FQ_EG_STREAMS; ++k) {
+        if (!spans[k].d_n || !spans[k].d_text || !spans[k].cap_bytes) continue;
+        t.text[k] = (uint8_t*)spans[k].d_text;
+        t.n[k] = spans[k].d_n;
+        t.cap[k] = spans[k].cap_bytes;
+        bound += members_of(spans[k].cap_bytes);
+    }
+    if (bound == 0) return hipMemsetAsync(d_totals, 0, FQ_EG_STREAMS * sizeof(unsigned long long), s);
+    const size_t most = std::min(bound, sc.members);
+    const int grid = (int)std::min<size_t>(most, (size_t)sc.grid);
+    hipLaunchKernelGGL(fq_deflate_spans_kernel, dim3(grid), dim3(FQ_DEFL_THREADS), FQ_DL_TOTAL, s, t,
+                       (unsigned long long)sc.members, level, sc.tok, sc.slots, sc.sizes);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int cgrid = (int)std::min<size_t>(most, (size_t)4 * sc.cus);
+    hipLaunchKernelGGL(fq_compact_spans_kernel, dim3(cgrid), dim3(256), 0, s, t, (unsigned long long)sc.members, sc.slots,
+                       sc.sizes, sc.total, d_err);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    // (d_totals may be the spans' length words: they are replaced only after both kernels have read them)
+    return hipMemcpyAsync(d_totals, sc.total, FQ_EG_STREAMS * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s);
 }
 
 struct fq_deflate {

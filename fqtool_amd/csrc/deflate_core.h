@@ -1,6 +1,8 @@
 // deflate_core.h -- the BGZF member compressor of deflate.hip: the Huffman length builder and the
 // other single-thread pieces as __host__ __device__ functions (the host runs them for checks), and
-// the per-member workgroup routine.  Included by deflate.hip only, after <hip/hip_runtime.h>.
+// the per-member workgroup routine, the compaction of a member, and the index arithmetic and walks
+// of the multi-span kernels.  Included by deflate.hip only, after <hip/hip_runtime.h>
+// (tools/micro/deflate_sim.cpp compiles it for the host).
 //
 // One 256-thread workgroup compresses one member (<= 65280 input bytes, whole in LDS):
 //   1. matches: the member is walked in sub-blocks of 256 positions, one position per thread.  In
@@ -58,6 +60,63 @@
 static_assert(FQ_DL_TOTAL <= 80 * 1024, "deflate workgroup must leave room for two per CU");
 
 enum { FQ_DM_CRC = 0, FQ_DM_HBITS, FQ_DM_HLIT, FQ_DM_HDIST, FQ_DM_HCLEN, FQ_DM_NSEQ, FQ_DM_BAD };
+
+// ---- several spans of one launch: the member index arithmetic -------------------------------------
+// The multi-span kernels (deflate.hip fq_deflate_spans_kernel / fq_compact_spans_kernel) number the
+// members of up to FQ_DEFL_SPANS texts with one global index g: span k's members are
+// [base[k], base[k + 1]), base[FQ_DEFL_SPANS] is their count.  Member g is compressed into scratch
+// slot g and compacted to its own span's buffer at the sum of the sizes of slots [first, g).
+// (No array here is indexed with a run-time value: on the device that would put it in scratch memory.)
+#define FQ_DEFL_SPANS 6            // = FQ_EG_STREAMS, the routed egress's streams
+#define FQ_DEFL_MEMBER_IN 65280    // = FQ_BGZF_IN
+struct fq_defl_layout {
+    unsigned long long len[FQ_DEFL_SPANS];       // each span's bytes, clamped to its capacity
+    unsigned long long base[FQ_DEFL_SPANS + 1];
+};
+struct fq_defl_place {
+    int span;                  // -1: g is no member
+    unsigned long long first;  // global index of the span's first member
+    unsigned long long at;     // byte offset of the member's input in its span
+    uint32_t len;              // its input bytes (1..65280)
+    bool last;                 // the span's last member
+};
+
+// n[k]: span k's length word as read, cap[k]: its capacity (0 for a span that is not there)
+__host__ __device__ inline void fq_defl_spans_layout(const unsigned long long (&n)[FQ_DEFL_SPANS],
+                                                     const unsigned long long (&cap)[FQ_DEFL_SPANS], fq_defl_layout& L) {
+    unsigned long long b = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 0; k < FQ_DEFL_SPANS; ++k) {
+        L.len[k] = n[k] < cap[k] ? n[k] : cap[k];
+        L.base[k] = b;
+        b += (L.len[k] + FQ_DEFL_MEMBER_IN - 1) / FQ_DEFL_MEMBER_IN;
+    }
+    L.base[FQ_DEFL_SPANS] = b;
+}
+
+__host__ __device__ inline fq_defl_place fq_defl_spans_place(const fq_defl_layout& L, unsigned long long g) {
+    fq_defl_place p{-1, 0, 0, 0, false};
+    if (g >= L.base[FQ_DEFL_SPANS]) return p;
+    unsigned long long len = 0, next = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 0; k < FQ_DEFL_SPANS; ++k) {
+        // (an empty span has base[k] == base[k + 1] and is never chosen)
+        const bool in = g >= L.base[k] && g < L.base[k + 1];
+        p.span = in ? k : p.span;
+        p.first = in ? L.base[k] : p.first;
+        len = in ? L.len[k] : len;
+        next = in ? L.base[k + 1] : next;
+    }
+    p.at = (g - p.first) * FQ_DEFL_MEMBER_IN;
+    const unsigned long long rest = len - p.at;
+    p.len = (uint32_t)(rest < FQ_DEFL_MEMBER_IN ? rest : FQ_DEFL_MEMBER_IN);
+    p.last = g + 1 == next;
+    return p;
+}
 
 // ---- Huffman code lengths: package-merge ------------------------------------------------------
 // 32-bit words of workspace fq_huff_code_lengths needs for n_sym symbols and max_len levels
@@ -523,4 +582,131 @@ __device__ inline uint32_t fq_deflate_member(uint8_t* lds, const uint8_t* src, u
         dst[18 + payload + k] = (uint8_t)((k < 4 ? crc : n) >> (8 * (k & 3)));
     }
     return member;
+}
+
+// ---- compaction -------------------------------------------------------------------------------------
+// Moves member g (scratch slot g, sizes[g] bytes) to its place in its stream: dst + the sizes of the
+// slots [first, g), first being the slot of the stream's first member.  Returns the stream offset
+// past the member (the same value in every thread).  A member that would not fit dst_cap (or whose
+// size is no member's) is not written.  part: 256 words of the workgroup's LDS.
+__device__ inline unsigned long long fq_compact_member(unsigned long long* part, const uint8_t* slots, const uint32_t* sizes,
+                                                       unsigned long long first, unsigned long long g, uint8_t* dst,
+                                                       unsigned long long dst_cap) {
+    const uint32_t tid = threadIdx.x;
+    unsigned long long sum = 0;
+    for (unsigned long long i = first + tid; i < g; i += 256) sum += sizes[i];
+    part[tid] = sum;
+    __syncthreads();
+    for (uint32_t s = 128; s > 0; s >>= 1) {
+        if (tid < s) part[tid] += part[tid + s];
+        __syncthreads();
+    }
+    const unsigned long long off = part[0];
+    __syncthreads();
+    const uint32_t sz = sizes[g];
+    const uint8_t* src = slots + g * FQ_DEFL_SLOT;
+    if (sz <= FQ_DEFL_SLOT && off + sz <= dst_cap) {
+        // 4 bytes a thread once the destination is aligned (the slot is; the stream offset is not)
+        const uint32_t lead = (uint32_t)((4 - ((uintptr_t)(dst + off) & 3)) & 3);
+        const uint32_t head = sz < lead ? sz : lead;
+        if (tid < head) dst[off + tid] = src[tid];
+        const uint32_t words = (sz - head) / 4;
+        uint32_t* d4 = (uint32_t*)(dst + off + head);
+        for (uint32_t i = tid; i < words; i += 256) {
+            const uint8_t* q = src + head + 4 * i;
+            d4[i] = (uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16 | (uint32_t)q[3] << 24;
+        }
+        const uint32_t done = head + 4 * words;
+        if (tid < sz - done) dst[off + done + tid] = src[done + tid];
+    }
+    return off + sz;
+}
+
+// ---- several spans by one launch: the two walks ----------------------------------------------------
+// members: the slots the scratch holds.  A member beyond them is skipped by both walks, and the
+// compaction then compacts nothing at all, writes 0 for every total and sets bit 1 of *err, so that
+// nothing of a pack with a skipped member is ever taken for a stream.
+struct fq_span_table {
+    uint8_t* text[FQ_DEFL_SPANS];                // the text in, the stream out (fq_deflate_bound(cap) bytes)
+    const unsigned long long* n[FQ_DEFL_SPANS];  // its length word (null: no such span)
+    unsigned long long cap[FQ_DEFL_SPANS];
+};
+
+__device__ inline void fq_span_layout(const fq_span_table& t, fq_defl_layout& L) {
+    unsigned long long n[FQ_DEFL_SPANS], cap[FQ_DEFL_SPANS];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 0; k < FQ_DEFL_SPANS; ++k) {
+        n[k] = t.n[k] ? *t.n[k] : 0;
+        cap[k] = t.n[k] ? t.cap[k] : 0;
+    }
+    fq_defl_spans_layout(n, cap, L);
+}
+
+__device__ inline uint8_t* fq_span_text(const fq_span_table& t, int span) {
+    uint8_t* p = nullptr;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 0; k < FQ_DEFL_SPANS; ++k) p = k == span ? t.text[k] : p;
+    return p;
+}
+
+// workgroup `block` of `nblocks`: its members compressed into their slots (lds: FQ_DL_TOTAL bytes,
+// tok: this workgroup's token array)
+__device__ inline void fq_deflate_spans_walk(uint8_t* lds, const fq_span_table& t, unsigned long long members, int level,
+                                             uint32_t* tok, uint8_t* slots, uint32_t* sizes, unsigned block, unsigned nblocks) {
+    fq_defl_layout L;
+    fq_span_layout(t, L);
+    // (32-bit indices: the slots' bytes, 64 KiB each, bound their count far below 2^32)
+    const uint32_t nmem = (uint32_t)(L.base[FQ_DEFL_SPANS] < members ? L.base[FQ_DEFL_SPANS] : members);
+    for (uint32_t g = block; g < nmem; g += nblocks) {
+        // (the layout is derived anew per member: six scalar loads, instead of its 13 words kept in
+        // registers across the member routine, which spilled scalar registers)
+        fq_span_layout(t, L);
+        const fq_defl_place p = fq_defl_spans_place(L, g);
+        const uint32_t sz = fq_deflate_member(lds, fq_span_text(t, p.span) + p.at, p.len, level, tok,
+                                              slots + (size_t)g * FQ_DEFL_SLOT);
+        if (threadIdx.x == 0) sizes[g] = sz;
+    }
+}
+
+// ... its members moved to their streams, each span's total written by the workgroup that moves
+// its last member (an empty or absent span's by workgroup 0); part: 256 words of LDS
+__device__ inline void fq_compact_spans_walk(unsigned long long* part, const fq_span_table& t, unsigned long long members,
+                                             const uint8_t* slots, const uint32_t* sizes, unsigned long long* totals, int* err,
+                                             unsigned block, unsigned nblocks) {
+    const uint32_t tid = threadIdx.x;
+    fq_defl_layout L;
+    fq_span_layout(t, L);
+    const unsigned long long nmem = L.base[FQ_DEFL_SPANS];
+    const bool over = nmem > members;
+    if (block == 0 && tid == 0) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int k = 0; k < FQ_DEFL_SPANS; ++k)
+            if (over || L.len[k] == 0) totals[k] = 0;
+        if (over && err) atomicOr(err, 2);
+    }
+    if (over) return;
+    for (unsigned long long g = block; g < nmem; g += nblocks) {
+        const fq_defl_place p = fq_defl_spans_place(L, g);
+        unsigned long long cap = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int k = 0; k < FQ_DEFL_SPANS; ++k) cap = k == p.span ? t.cap[k] : cap;
+        // (the span's buffer: fq_deflate_bound(cap))
+        const unsigned long long dst_cap = cap + 31 * ((cap + FQ_DEFL_MEMBER_IN - 1) / FQ_DEFL_MEMBER_IN);
+        const unsigned long long end = fq_compact_member(part, slots, sizes, p.first, g, fq_span_text(t, p.span), dst_cap);
+        if (p.last && tid == 0) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+            for (int k = 0; k < FQ_DEFL_SPANS; ++k)
+                if (k == p.span) totals[k] = end;
+        }
+    }
 }

@@ -459,6 +459,9 @@ static int check_err(fq_engine* e) {
     return FQ_OK;
 }
 
+// gz on: an output buffer takes the BGZF stream of its text in place
+static size_t out_alloc(const fq_engine* e, size_t bytes) { return e->gz_level ? fq_deflate_bound(bytes) : bytes; }
+
 // Raw packs' copies back, exactly sized: a pack's kernels end by copying its output sizes to the
 // host (on the compute stream, event ev_kern); once they are in, its text + adapter entries are
 // copied back on the out stream (in submission order; the link chain orders the copies of engines
@@ -486,7 +489,7 @@ static int issue_copies(fq_engine* e, int upto) {
             for (int k = 0; k < FQ_EG_STREAMS && s.eg_out; ++k) {  // a routed pack: each open stream's text
                 // (a total above the caller's capacity copies nothing and fails the pack at retire)
                 const size_t bytes = (size_t)s.h_egtotal[k];
-                if (bytes && s.eg_out->text[k] && bytes <= s.eg_out->cap[k] && bytes <= s.eg_cap[k])
+                if (bytes && s.eg_out->text[k] && bytes <= s.eg_out->cap[k] && bytes <= out_alloc(e, s.eg_cap[k]))
                     HIP_TRY(e, hipMemcpyAsync(s.eg_out->text[k], s.d_eg[k], bytes, hipMemcpyDeviceToHost, e->s_out));
             }
             for (int m = 0; m < 2 && s.reg_out; ++m) {  // a routed raw pack: its trimmed-adapter entries
@@ -535,7 +538,7 @@ static int retire_slot(fq_engine* e, int k) {
         s.reg_out = nullptr;
         for (int k = 0; k < FQ_EG_STREAMS; ++k) {
             o->bytes[k] = s.h_egtotal[k];
-            if (o->bytes[k] > o->cap[k] || o->bytes[k] > s.eg_cap[k]) {
+            if (o->bytes[k] > o->cap[k] || o->bytes[k] > out_alloc(e, s.eg_cap[k])) {
                 o->bytes[k] = 0;
                 return fail(e, FQ_E_INVALID, "routed pack: a stream exceeds its buffer");
             }
@@ -568,9 +571,7 @@ static size_t merged_cap(uint64_t text1, uint64_t text2, size_t pairs) {
     return (size_t)text1 + (size_t)text2 + 24 * pairs + kTextSlack;
 }
 
-// gz on: an output buffer takes the BGZF stream of its text in place, and the scratch covers the
-// largest text (growing it waits for the device)
-static size_t out_alloc(const fq_engine* e, size_t bytes) { return e->gz_level ? fq_deflate_bound(bytes) : bytes; }
+// gz on: the scratch covers the largest text (growing it waits for the device)
 static int ensure_gz(fq_engine* e, size_t text_bytes) {
     if (!e->gz_level) return FQ_OK;
     HIP_TRY(e, fq_deflate_scratch_ensure(e->gz, text_bytes, e->cus));
@@ -1000,6 +1001,13 @@ size_t fq_egress_bound_umi(int32_t stream, uint64_t text_bytes1, uint64_t text_b
     }
 }
 
+// gz on: what the open streams of one pack hold together (include/fqengine.h, "device BGZF"), as the
+// bytes to size the compressor's scratch for: a member more per open stream for the short last ones
+static size_t egress_gz_scratch_bytes(const fq_engine* e, uint64_t text1, uint64_t text2, uint64_t n) {
+    return fq_egress_bound_umi(FQ_EG_FAILED, text1, text2, n, e->umi_on ? &e->umi : nullptr) +
+           (size_t)__builtin_popcount(e->eg_open) * FQ_BGZF_IN;
+}
+
 // the description against the engine's params (Options::umi_front)
 static bool umi_matches(const fq_params& p, const fq_umi& u) {
     const int front = u.not_trim ? 0 : u.length + u.skip;
@@ -1069,10 +1077,21 @@ static int ensure_egress_caps(fq_engine* e, Slot& s, uint64_t text1, uint64_t te
             s.d_eg[k] = nullptr;
             s.eg_cap[k] = 0;
             const size_t cap = need + need / 8;
-            HIP_TRY(e, hipMalloc(&s.d_eg[k], cap));
+            HIP_TRY(e, hipMalloc(&s.d_eg[k], out_alloc(e, cap)));
             s.eg_cap[k] = cap;
         }
     }
+    return ensure_gz(e, egress_gz_scratch_bytes(e, text1, text2, (uint64_t)n));
+}
+
+// gz on: every open stream's text (d_egtotal[q] bytes, at most bound[q]) -> BGZF members in place by
+// one pair of launches, d_egtotal[q] = their bytes; a pack whose members exceed the scratch sets bit 1
+// of the slot's error word
+static int launch_gz_streams(fq_engine* e, Slot& s, const size_t (&bound)[FQ_EG_STREAMS]) {
+    fq_deflate_span sp[FQ_EG_STREAMS] = {};
+    for (int q = 0; q < FQ_EG_STREAMS; ++q)
+        if ((e->eg_open >> q) & 1u) sp[q] = fq_deflate_span{s.d_eg[q], s.d_egtotal + q, std::min(bound[q], s.eg_cap[q])};
+    HIP_TRY(e, fq_launch_deflate_spans(e->gz, sp, e->gz_level, s.d_egtotal, s.d_err, e->stream));
     return FQ_OK;
 }
 
@@ -1082,7 +1101,6 @@ int fq_engine_submit_text_routed(fq_engine* e, const fq_text_batch* tb, fq_read_
     const bool pe = e->p.paired;
     const int mates = pe ? 2 : 1;
     if (!e->eg_on) return fail(e, FQ_E_INVALID, "routed text pack without fq_engine_set_egress");
-    if (e->gz_level) return fail(e, FQ_E_INVALID, "routed text packs take no device BGZF output");
     if (e->raw) return fail(e, FQ_E_INVALID, "routed text pack inside a raw stream");
     if (e->cut_armed) return fail(e, FQ_E_INVALID, "routed text packs take no pack cuts");
     if (tb->n < 0 || tb->n > e->max_batch || tb->stride <= 0 || tb->stride > e->max_stride || (tb->stride & 15))
@@ -1093,13 +1111,16 @@ int fq_engine_submit_text_routed(fq_engine* e, const fq_text_batch* tb, fq_read_
     for (int m = 0; m < mates; ++m)
         if (tb->n > 0 && (!tb->text[m] || !tb->rec[m])) return fail(e, FQ_E_INVALID, "missing text pack arrays");
     // every open stream needs a buffer of at least its bound, before anything is launched or copied
+    // (gz on: the bound of its BGZF stream)
+    size_t bound[FQ_EG_STREAMS] = {};
     for (int k = 0; k < FQ_EG_STREAMS; ++k) {
         out->bytes[k] = 0;
         if (!((e->eg_open >> k) & 1u)) continue;
         const size_t need = fq_egress_bound_umi(k, tb->text_bytes[0], pe ? tb->text_bytes[1] : 0, (uint64_t)tb->n, umi_of(e));
         if (e->umi_on && need > 0xFFFFFFFFull) return fail(e, FQ_E_INVALID, "routed text pack: a UMI-tagged stream's bound exceeds the 32-bit cursors (submit smaller packs)");
-        if (!out->text[k] || out->cap[k] < need)
+        if (!out->text[k] || out->cap[k] < out_alloc(e, need))
             return fail(e, FQ_E_INVALID, "routed text pack: an open stream's buffer is missing or below fq_egress_bound");
+        bound[k] = need;
     }
     if (tb->n == 0) {
         e->pending.push_back(Pending{seq_no, -1, true, 0});
@@ -1160,8 +1181,9 @@ int fq_engine_submit_text_routed(fq_engine* e, const fq_text_batch* tb, fq_read_
     for (int q = 0; q < FQ_EG_STREAMS; ++q) st.size[q] = s.d_egsize[q], st.off[q] = s.d_egoff[q], st.out[q] = s.d_eg[q];
     st.total = s.d_egtotal;
     HIP_TRY(e, fq_launch_egress(a, st, s.d_scan, s.scan_bytes, e->stream));
-    // records, sizes and the error word behind the kernels; each stream's text follows once the
-    // sizes are in (issue_copies)
+    if (e->gz_level && (rc = launch_gz_streams(e, s, bound)) != FQ_OK) return rc;
+    // records, sizes and the error word behind the kernels; each stream's text (gz: its members)
+    // follows once the sizes are in (issue_copies)
     const size_t nres = (size_t)tb->n * mates;
     HIP_TRY(e, hipMemcpyAsync(results, s.d_res, nres * sizeof(fq_read_result), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipMemcpyAsync(s.h_egtotal, s.d_egtotal, FQ_EG_STREAMS * sizeof(unsigned long long), hipMemcpyDeviceToHost,
@@ -1469,7 +1491,6 @@ int fq_engine_raw_launch(fq_engine* e, fq_raw_result* r, fq_raw_out* out, uint64
 int fq_engine_raw_launch_routed(fq_engine* e, fq_raw_result* r, fq_raw_egress_out* out, uint64_t seq_no) {
     if (!e || !r || !out) return FQ_E_INVALID;
     if (!e->eg_on) return fail(e, FQ_E_INVALID, "routed raw pack without fq_engine_set_egress");
-    if (e->gz_level) return fail(e, FQ_E_INVALID, "routed raw packs take no device BGZF output");
     if (e->raw_queued.empty()) return fail(e, FQ_E_INVALID, "fq_engine_raw_launch_routed without an enqueued window");
     if (e->cut_armed) return fail(e, FQ_E_INVALID, "routed raw packs take no pack cuts");
     HIP_TRY(e, hipSetDevice(e->device));
@@ -1482,13 +1503,16 @@ int fq_engine_raw_launch_routed(fq_engine* e, fq_raw_result* r, fq_raw_egress_ou
     const int n = r->pairs;
     // every open stream (and, with -a, each mate's entries) needs a buffer of at least its bound; a
     // refusal leaves the window enqueued
+    // (gz on: the bound of its BGZF stream)
+    size_t bound[FQ_EG_STREAMS] = {};
     for (int q = 0; q < FQ_EG_STREAMS; ++q) {
         out->eg.bytes[q] = 0;
         if (!((e->eg_open >> q) & 1u) || n <= 0) continue;
         const size_t need = fq_egress_bound_umi(q, r->text_bytes[0], pe ? r->text_bytes[1] : 0, (uint64_t)n, umi_of(e));
         if (e->umi_on && need > 0xFFFFFFFFull) return fail(e, FQ_E_INVALID, "routed raw pack: a UMI-tagged stream's bound exceeds the 32-bit cursors (use smaller windows and max_batch)");
-        if (!out->eg.text[q] || out->eg.cap[q] < need)
+        if (!out->eg.text[q] || out->eg.cap[q] < out_alloc(e, need))
             return fail(e, FQ_E_INVALID, "routed raw pack: an open stream's buffer is missing or below fq_egress_bound");
+        bound[q] = need;
     }
     for (int m = 0; m < 2; ++m) {
         out->adapter_bytes[m] = 0;
@@ -1538,7 +1562,8 @@ int fq_engine_raw_launch_routed(fq_engine* e, fq_raw_result* r, fq_raw_egress_ou
     for (int q = 0; q < FQ_EG_STREAMS; ++q) st.size[q] = s.d_egsize[q], st.off[q] = s.d_egoff[q], st.out[q] = s.d_eg[q];
     st.total = s.d_egtotal;
     HIP_TRY(e, fq_launch_egress(a, st, s.d_scan, s.scan_bytes, e->stream));
-    // the trimmed-adapter entries per mate, into their own buffer (corrected pairs: the corrected bytes)
+    if (e->gz_level && (rc = launch_gz_streams(e, s, bound)) != FQ_OK) return rc;
+    // the trimmed-adapter entries per mate, uncompressed, into their own buffer (corrected pairs: the corrected bytes)
     for (int m = 0; m < mates && e->p.adapter_trimming; ++m)
         HIP_TRY(e, fq_launch_egress_adapters(a, m, s.d_tsize[m], s.d_toff[m], s.d_scan, s.scan_bytes, s.d_ad[m],
                                              (unsigned long long)s.ad_cap, s.d_total + 2 + m, e->stream));
@@ -1578,6 +1603,7 @@ int fq_engine_set_gz_out(fq_engine* e, int32_t level) {
         // the output buffers are sized for the stream's bound while gz is on: re-made on next use
         for (Slot& s : e->slots) {
             s.text_cap[0] = s.text_cap[1] = 0;
+            for (int k = 0; k < FQ_EG_STREAMS; ++k) s.eg_cap[k] = 0;  // (ensure_egress_caps re-makes the streams' buffers)
             s.raw_ready = false;
         }
         if (!level) {
@@ -1621,6 +1647,7 @@ int fq_engine_poll(fq_engine* e, int wait, uint64_t* seq_no) {
     const Pending done = q;
     e->pending.pop_front();
     if (seq_no) *seq_no = done.seq_no;
+    if (done.err & 2) return fail(e, FQ_E_INVALID, "device BGZF: the pack's members exceed the compressor's scratch");
     if (done.err) return fail(e, FQ_E_TOO_LONG, "a read is longer than max_cycles or the row stride");
     return 1;
 }

@@ -117,7 +117,7 @@ struct fq_deflate_scratch {
     uint32_t* tok = nullptr;
     uint8_t* slots = nullptr;
     uint32_t* sizes = nullptr;
-    unsigned long long* total = nullptr;
+    unsigned long long* total = nullptr;  // [FQ_EG_STREAMS]
     size_t members = 0;  // members the slots hold
     int grid = 0;        // workgroups the token arrays serve
     int cus = 0;
@@ -129,6 +129,19 @@ void fq_deflate_scratch_free(fq_deflate_scratch& sc);
 // compacted only after all are compressed), their bytes to *d_total (which may be d_n)
 hipError_t fq_launch_deflate(const fq_deflate_scratch& sc, const void* d_text, const unsigned long long* d_n, size_t cap_bytes,
                              int level, void* d_dst, size_t dst_cap, unsigned long long* d_total, hipStream_t s);
+// The same for up to FQ_EG_STREAMS texts of one pack by one pair of launches (a routed pack's
+// streams, whose real sizes only the device knows): spans[k] with d_n null is not there.  Each text
+// becomes its members in place (its buffer holds fq_deflate_bound(cap_bytes)), d_totals[k] = their
+// bytes, 0 for an empty or absent span; d_totals may be the array the d_n point into.  The members of
+// all spans share the scratch: should they exceed sc.members, nothing is compacted, every total is 0
+// and bit 1 of *d_err is set (d_err may be null).
+struct fq_deflate_span {
+    void* d_text;
+    const unsigned long long* d_n;
+    size_t cap_bytes;
+};
+hipError_t fq_launch_deflate_spans(const fq_deflate_scratch& sc, const fq_deflate_span* spans, int level,
+                                   unsigned long long* d_totals, int* d_err, hipStream_t s);
 // Raw FASTQ streams (raw.hip): per (window, mate) device state of the record indexing
 struct fq_raw_state {
     uint32_t text_start;  // buffer offset of the window's text (the carried bytes first)

@@ -757,7 +757,17 @@ uint32_t OutputSet::egress_mask() const {
     return m;
 }
 
-void OutputSet::write_routed(const fq_egress_out& out, std::function<void()> done) {
+bool OutputSet::routed_outputs_gzip() const {
+    const AsyncWriter* w[FQ_EG_STREAMS] = {};
+    w[FQ_EG_OUT1] = w1_.get(), w[FQ_EG_OUT2] = w2_.get(), w[FQ_EG_MERGED] = wm_.get();
+    w[FQ_EG_UNPAIRED1] = wu1_.get(), w[FQ_EG_UNPAIRED2] = wu2_.get(), w[FQ_EG_FAILED] = wf_.get();
+    const uint32_t mask = egress_mask();
+    for (int s = 0; s < FQ_EG_STREAMS; ++s)
+        if (((mask >> s) & 1u) && !w[s]->gzip()) return false;
+    return mask != 0;
+}
+
+void OutputSet::write_routed(const fq_egress_out& out, std::function<void()> done, bool members) {
     AsyncWriter* w[FQ_EG_STREAMS] = {};
     const uint32_t mask = egress_mask();
     w[FQ_EG_OUT1] = w1_.get(), w[FQ_EG_OUT2] = w2_.get(), w[FQ_EG_MERGED] = wm_.get();
@@ -776,7 +786,7 @@ void OutputSet::write_routed(const fq_egress_out& out, std::function<void()> don
     for (int s = 0; s < FQ_EG_STREAMS; ++s) {
         if (!((mask >> s) & 1u)) continue;
         try {
-            w[s]->write_raw(out.text[s], (size_t)out.bytes[s], fin, false);
+            w[s]->write_raw(out.text[s], (size_t)out.bytes[s], fin, members);
         } catch (...) {  // (write_raw has called fin before it throws, so the count still reaches zero)
             if (!err) err = std::current_exception();
         }
@@ -1012,6 +1022,8 @@ bool Sink::plain_pair_outputs() const { return outs_ && !merge_ && outs_->plain_
 
 uint32_t Sink::egress_mask() const { return outs_ ? outs_->egress_mask() : 0u; }
 
+bool Sink::routed_outputs_gzip() const { return outs_ && outs_->routed_outputs_gzip(); }
+
 void Sink::consume_text(const Pack& pk, std::function<void()> done) {
     if (split_) {  // (the split writers are synchronous)
         if (!pk.cut || pk.first_item != pairs_) throw std::runtime_error("split output: a text pack without its cut table");
@@ -1025,7 +1037,7 @@ void Sink::consume_text(const Pack& pk, std::function<void()> done) {
         return;
     }
     pairs_ += (uint64_t)pk.n;
-    if (pk.routed) outs_->write_routed(pk.eout, std::move(done));
+    if (pk.routed) outs_->write_routed(pk.eout, std::move(done), pk.gz_members);
     else if (pk.zc) outs_->write_text_segs(pk.segs[0], pk.segs[1], std::move(done));
     else if (merge_) outs_->write_merged_text(pk.out_text[0].data(), pk.tout.bytes[0], std::move(done), pk.gz_members);
     else
@@ -1638,11 +1650,12 @@ struct Lane {
                 pk.eout = fq_egress_out{};
                 for (int s = 0; s < FQ_EG_STREAMS; ++s) {
                     if (!((eg_open >> s) & 1u)) continue;
-                    const size_t cap = eg_bound(s, pk.span_bytes[0], pk.paired ? pk.span_bytes[1] : 0, (uint64_t)pk.n);
+                    const size_t cap = out_cap(eg_bound(s, pk.span_bytes[0], pk.paired ? pk.span_bytes[1] : 0, (uint64_t)pk.n));
                     pk.eg_text[s].resize_uninit(cap);
                     pk.eout.text[s] = pk.eg_text[s].data();
                     pk.eout.cap[s] = cap;
                 }
+                pk.gz_members = gz_level != 0;
                 if (fq_engine_submit_text_routed(e, &tb, pk.results(), &pk.eout, pk.seq_no) != FQ_OK)
                     throw std::runtime_error(std::string("fq_engine_submit_text_routed: ") + fq_engine_last_error(e));
                 submit_s += since(e0);
@@ -1997,12 +2010,13 @@ struct Lane {
                         const uint64_t t1 = cin[0] + w.n[0], t2 = mates == 2 ? cin[1] + w.n[1] : 0;
                         for (int s = 0; s < FQ_EG_STREAMS; ++s) {
                             if (!((eg_open >> s) & 1u)) continue;
-                            const size_t cap = eg_bound(s, t1, t2, (uint64_t)target);
+                            const size_t cap = out_cap(eg_bound(s, t1, t2, (uint64_t)target));
                             pk->eg_text[s].reserve(cap + cap / 8);
                             pk->eg_text[s].resize_uninit(cap);
                             pk->reout.eg.text[s] = pk->eg_text[s].data();
                             pk->reout.eg.cap[s] = cap;
                         }
+                        pk->gz_members = gz_level != 0;
                         // (the entries' worst case is the whole input, their usual size a few percent of
                         // it: ordinary memory, Pack::text, which a raw pack does not use otherwise)
                         for (int m = 0; m < mates; ++m) {
@@ -2605,7 +2619,7 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
                                split_ok && ingest_ok &&
                                (o.merge ? paired && !o.merge_out.empty()
                                         : !o.out1.empty() && (!paired || !o.out2.empty()));
-        // (the records-only egress and device BGZF stay with the plain pair / merged outputs)
+        // (the records-only egress stays with the plain pair / merged outputs)
         const bool routed = text_mode && eg_wanted;
         const uint32_t outs_mask = outs.egress_mask();  // (for the closing log line: the Sink is closed by then)
         // records-only raw packs to plain outputs go out as byte ranges of their windows (zero copy)
@@ -2638,12 +2652,15 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
                     pre_gz[m]->prefetch();
         }
         // FQ_GZ_DEVICE=1: the engines compress the output text of text / raw packs (BGZF members, -z
-        // as the level) when every output those packs feed is .gz; host packs, and engines without
-        // the call, keep the host's compression
+        // as the level) when every output those packs feed is .gz (a routed run: every stream that
+        // has a writer; the switch is per engine, so one plain stream keeps the host's compression
+        // for all); host packs, and engines without the call, keep the host's compression
         const char* gzd_env = std::getenv("FQ_GZ_DEVICE");
         const bool gz_device = gzd_env && std::string(gzd_env) == "1" && fq_engine_set_gz_out && fq_deflate_bound &&
-                               text_mode && !routed && !split && o.compression >= 1 && o.compression <= 9 &&
-                               (o.merge ? ends_with_gz(o.merge_out) : ends_with_gz(o.out1) && (!paired || ends_with_gz(o.out2)));
+                               text_mode && !split && o.compression >= 1 && o.compression <= 9 &&
+                               (routed    ? outs.routed_outputs_gzip()
+                                : o.merge ? ends_with_gz(o.merge_out)
+                                          : ends_with_gz(o.out1) && (!paired || ends_with_gz(o.out2)));
         for (int g = 0; g < G; ++g) {
             lanes.emplace_back(new Lane(devices[(size_t)g], depth));
             lanes.back()->gz_level = gz_device ? o.compression : 0;
@@ -2990,7 +3007,8 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
             " s; JSON report " + o.json_file + ", HTML report " + o.html_file +
             (o.ora && ora_devices_given > 1 ? "; --ora: one engine on device " + std::to_string(devices[0]) + " of the " +
                                                   std::to_string(ora_devices_given) + " given (the sampling counts one stream)"
-                                            : std::string()));
+                                            : std::string()) +
+            (gz_device ? "; device BGZF" : ""));
         if (std::getenv("FQ_TIMING_MONO")) {  // (profiling: steady-clock stamps, to time exec and exit from outside)
             auto mono = [](std::chrono::steady_clock::time_point t) {
                 return std::to_string(std::chrono::duration<double>(t.time_since_epoch()).count());

@@ -46,8 +46,10 @@ class OutputSet {
     // routed egress (fq_engine_set_egress): the streams that have a writer, as FQ_EG_* bits (a
     // paired run writes the pair outputs only with both writers), and a routed pack's streams handed
     // to them; `done` runs once every writer is through with its text
+    // (members: every stream's bytes are gzip members the engine compressed, as write_text's)
     uint32_t egress_mask() const;
-    void write_routed(const fq_egress_out& out, std::function<void()> done);
+    bool routed_outputs_gzip() const;  // every one of those streams is a gzip output (and there is one)
+    void write_routed(const fq_egress_out& out, std::function<void()> done, bool members = false);
     void close();  // flushes and closes every file
 
    private:
@@ -77,6 +79,7 @@ class Sink {
     void consume_text(const Pack& pk, std::function<void()> done);
     bool plain_pair_outputs() const;  // text packs may go out as byte ranges (Pack::zc)
     uint32_t egress_mask() const;     // the writers as FQ_EG_* bits (0 with -s / -S: no routed egress)
+    bool routed_outputs_gzip() const; // all of them gzip outputs: routed packs may come back as BGZF members
     void close();
 
    private:

@@ -615,6 +615,25 @@ double fq_ora_last_kernel_ms(const fq_ora* h);
  * egress (out->results set) is refused while gz is on.  Level 0 (the default) turns it off;
  * fq_engine_submit and fq_engine_process* are unaffected.  The device scratch is allocated with
  * the slots' output buffers, nothing while gz is off.
+ * Routed packs (fq_engine_submit_text_routed, fq_engine_raw_launch_routed, below) are compressed
+ * likewise: behind the egress kernel one pair of launches compresses every open stream of the pack,
+ * out->text[s] receives stream s's members and out->bytes[s] their byte count (0 for a stream
+ * nothing was routed to: no bytes, no member), and the copies back are exactly the members.  The
+ * caller's cap[s] must then be at least fq_deflate_bound(fq_egress_bound_umi(s, ...)), else the call
+ * is refused (FQ_E_INVALID) before anything is launched or copied (a raw window stays enqueued).  A
+ * routed raw pack's adapter entries stay uncompressed in adapters[m].
+ * The streams' real sizes are known only on the device, and their bounds add up to several times the
+ * pack's input (FAILED and MERGED may each take both mates), so the compressor's scratch is sized by
+ * what the six streams can hold together.  Per pair the egress writes every read to at most one
+ * stream: a read is its input record (name, bases, strand line, qualities and four terminators, of
+ * which an input may lack the last), plus a blank and a failure tag of at most 22 bytes in FAILED,
+ * plus its UMI tag; a merged pair is written once, with mate 1's name and strand line, at most both
+ * mates' bases and a "_merged_<m1>_<m2>" tag of less than 24 bytes.  That is FAILED's own bound with
+ * every read in it, so over all streams
+ *     sum of bytes[s] before compression <= fq_egress_bound_umi(FQ_EG_FAILED, text_bytes1, text_bytes2, n, u)
+ * and the members number at most ceil(that / FQ_BGZF_IN) plus one per open stream (each stream's
+ * last member may be short).  Should a pack ever exceed the scratch, no member is taken for a write:
+ * fq_engine_poll fails the pack with FQ_E_INVALID and every bytes[s] is 0.
  * fq_deflate_code_lengths runs the kernels' own length builder on the host (optimal length-limited
  * code lengths by package-merge: 0 for unused symbols; n_sym <= 288, max_len <= 15, the sum of
  * freq times max_len below 2^32, else FQ_E_INVALID). */
@@ -654,7 +673,9 @@ int fq_engine_set_gz_out(fq_engine* e, int32_t level);                  /* 0 (de
  * default) turns the routed egress off; fq_engine_submit_text, fq_engine_raw_begin and
  * fq_engine_raw_launch write and refuse as before (fq_engine_raw_begin takes -c and
  * --discard_unmerged once an egress is set, for fq_engine_raw_launch_routed below), and the routed
- * calls are refused (FQ_E_INVALID) while no egress is set or device BGZF (fq_engine_set_gz_out) is on.
+ * calls are refused (FQ_E_INVALID) while no egress is set.  With device BGZF on (fq_engine_set_gz_out)
+ * they write every open stream as BGZF members and the capacities below become those of the members,
+ * fq_deflate_bound(fq_egress_bound(...)) ("device BGZF" above).
  * fq_egress_bound (no device needed) is the capacity stream s needs for a pack of n records whose
  * mates span text_bytes1 / text_bytes2 (0 for single end) bytes of input text: a record's output is
  * its input (plus the final line terminator an input may lack); a FAILED record adds a blank and a

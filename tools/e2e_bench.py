@@ -77,8 +77,12 @@ def masked_json(path):
     return j
 
 
-def run(tool, r1, r2, d, tag, cfg, workers, extra=(), null_out=False):
+def run(tool, r1, r2, d, tag, cfg, workers, extra=(), null_out=False, gz_out=False):
     o = {k: os.path.join(d, f"{tag}_{k}") for k in ("o1.fq", "o2.fq", "m.fq", "r.json", "r.html")}
+    if gz_out:  # .gz outputs; {out} in an extra option names a further .gz output next to them
+        for k in ("o1.fq", "o2.fq", "m.fq"):
+            o[k] += ".gz"
+        extra = [x.replace("{out}", os.path.join(d, tag)) for x in extra]
     if null_out:
         for k in ("o1.fq", "o2.fq", "m.fq"):
             o[k] = "/dev/null"
@@ -172,6 +176,8 @@ def main():
     ap.add_argument("--pause", type=float, default=0.0, help="seconds between fqtool-amd runs")
     ap.add_argument("--tools", default=None, help="comma list of name=path binaries run in turn for every variant and "
                     "repeat (A/B against another build; default: this tree's fqtool)")
+    ap.add_argument("--gz-out", action="store_true", help="name the FASTQ outputs .gz (put TMPDIR on tmpfs); "
+                    "'{out}' in --extra / --variants becomes a path prefix for further outputs, e.g. --failed_out {out}_f.fq.gz")
     ap.add_argument("--gz", default=None, choices=["bgzf", "gzip"], help="compressed inputs: BGZF or one gzip stream")
     args = ap.parse_args()
     tmp = tempfile.mkdtemp(prefix="fqe2e_")
@@ -195,7 +201,7 @@ def main():
             if args.pause:
                 time.sleep(args.pause)
             extra = (["--devices", args.devices] if args.devices else []) + v.split()
-            wall, inner, o_ours = run(binary, r1, r2, tmp, "amd", args.config, w, extra, args.null_out)
+            wall, inner, o_ours = run(binary, r1, r2, tmp, "amd", args.config, w, extra, args.null_out, args.gz_out)
             line = {"tool": name, "config": args.config, "pairs": args.pairs, "fastq_GB": round(gb, 3),
                     "wall_s": round(wall, 3), "Mreads_s": round(reads / wall / 1e6, 3),
                     "fastq_GB_s": round(gb / wall, 3), "workers": w, "devices": args.devices, "extra": v,
