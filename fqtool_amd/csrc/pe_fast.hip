@@ -199,6 +199,13 @@ __device__ __forceinline__ uint32_t pairrev(uint32_t x) {
     return ((y >> 1) & 0x55555555u) | ((y & 0x55555555u) << 1);
 }
 
+// one v_bfrev, kept opaque: with __builtin_bitreverse32 at the Stats pass's read-2 chunks the
+// FULL -c / UMI instantiations spill a VGPR
+__device__ __forceinline__ uint32_t bfrev(uint32_t x) {
+    asm("v_bfrev_b32 %0, %1" : "=v"(x) : "v"(x));
+    return x;
+}
+
 __device__ __forceinline__ uint32_t fold2(uint32_t x) { return (x | (x >> 1)) & 0x55555555u; }
 
 // low `n` two-bit positions (spaced mask), n may be <= 0 or >= 16
@@ -974,6 +981,16 @@ __device__ __forceinline__ void hadd(uint32_t* base, int word, unsigned long lon
 // histogram slot (A C T G N) -> Stats base class (byte & 7), src/stats.cpp:249
 __device__ __forceinline__ int slot_class(int s) { return (0x67431 >> (4 * s)) & 0xF; }
 
+// Removed-mode rows: the slot (0-3 removed, + 4 kept) of forward base code s (A C T G) in a mate's rows.
+// Read 1's are labelled by the code.  Read 2's column holds the reverse complement, and the Stats pass
+// takes a chunk of it through one v_bfrev: that restores the position order and leaves each field
+// bit-swapped and still complemented, so forward code c arrives as bitswap(c ^ 2) -- A C T G in slots
+// 1 3 0 2 -- and is counted there.  An N is 3 either way and keeps its + 5 (kRNSlot).  Whatever
+// addresses these rows by base (the flush, -c) goes through this table.
+__host__ __device__ constexpr int rem_slot(int mate, int s) { return mate ? (0x2031 >> (4 * s)) & 3 : s; }
+static_assert(rem_slot(1, 0) == 1 && rem_slot(1, 1) == 3 && rem_slot(1, 2) == 0 && rem_slot(1, 3) == 2 && rem_slot(0, 2) == 2,
+              "rem_slot: bitswap(c ^ 2)");
+
 // LEAN: the option set of the headline workloads (no trimming/cutting windows, -e, polyX, adapter
 // sequences, maxLen or low-complexity filter), instantiated separately so the hot loop carries
 // neither their code nor their parameters.
@@ -1062,7 +1079,7 @@ __device__ inline bool correct_pair_fast(const fq_params& p, uint32_t* col, uint
             const_cast<uint8_t*>((mate ? b.seq2 : b.seq1) + roff)[(P >> 4) * (FQ_TILE_READS * FQ_CHUNK) + (P & 15)] =
                 nN ? (uint8_t)'N' : (uint8_t)"ACTG"[fn];
             if (removed) {
-                const int so = oN ? kRNSlot : (int)fo, sn = nN ? kRNSlot : (int)fn;
+                const int so = oN ? kRNSlot : rem_slot(mate, (int)fo), sn = nN ? kRNSlot : rem_slot(mate, (int)fn);
                 atomicAdd(reinterpret_cast<unsigned long long*>(lds + rem_block + rcell(P, so)), kCount1 | (unsigned long long)xo);
                 atomicAdd(reinterpret_cast<unsigned long long*>(lds + rem_block + rcell(P, sn)), 0ull - (kCount1 | (unsigned long long)xn));
             } else {
@@ -1975,10 +1992,9 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
             const int cstep = rc ? -64 : 64;
             [[maybe_unused]] auto fwd_at = [&](const uint32_t* wp_) {
                 uint32_t cw = wp_[kFC * 64], nw = wp_[kFN * 64];
-                if (rc) {
-                    cw = pairrev(cw);
-                    nw = pairrev(nw);
-                    cw ^= 0xAAAAAAAAu & ~(nw << 1);  // complement back, N stays code 3
+                if (rc) {  // position order only: the codes stay relabelled (rem_slot), the N flags at the odd bits
+                    cw = bfrev(cw);
+                    nw = bfrev(nw);
                 }
                 return Fwd{cw, nw};
             };
@@ -2005,10 +2021,9 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                     Fwd f = fn;
                     if constexpr (kPf2) {
                         uint32_t fc = rw0c, fnw = rw0n;
-                        if (rc) {
-                            fc = pairrev(fc);
-                            fnw = pairrev(fnw);
-                            fc ^= 0xAAAAAAAAu & ~(fnw << 1);  // complement back, N stays code 3
+                        if (rc) {  // (as fwd_at)
+                            fc = bfrev(fc);
+                            fnw = bfrev(fnw);
                         }
                         f = Fwd{fc, fnw};
                         rw0c = rw1c;
@@ -2028,7 +2043,7 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                         fn = fwd_at(cwp);
                     }
                     const int vl = L - 16 * F;
-                    // slot 4 * kept + code; an N (code 3) reads as a G here
+                    // slot 4 * kept + code (read 2: the reversed field, rem_slot); an N is 3 here either way
                     // kept nibbles: ~(~0 << s), s = clamp(4 wlen - 64 F, 0, 63) (one v_med3); the
                     // codes spread to nibbles for both halves at once by 64-bit shifts, masked by
                     // one v_bitop3 per word, the kept bit or-ed in by another
@@ -2048,11 +2063,23 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                         lo = (~(uint32_t)km & m44) | z0;
                         hi = (~(uint32_t)(km >> 32) & m44) | z1;
                     }
-                    // N bases: their slot kRNSlot + 4 * kept is the G slot + 5, one nibble add (staging
+                    // N bases: their slot kRNSlot + 4 * kept is slot 3 + 5, one nibble add (staging
                     // kept N flags only inside the read)
                     if (__any(f.n != 0)) {
                         // (n0 nibbles are 0 or 1: n0 | n0 << 2 is 5 n0, one v_lshl_or)
-                        const uint32_t n0 = spread2to4(f.n), n1 = spread2to4(f.n >> 16);
+                        // (read 2: the reversed word holds the flags at the odd bits, (rev >> 1) & 0x5555...;
+                        // the other bit of a field, the lowercase flag, is clear in every valid lane by
+                        // now -- cleared above or its pair handed over -- so one fold serves both mates)
+                        const uint32_t nf = fold2(f.n);
+                        // (the flags go to nibbles as the codes did: two v_perm, two 64-bit shifts)
+                        const uint32_t x0 = __builtin_amdgcn_perm(nf, nf, 0x0c010c00u);
+                        const uint32_t x1 = __builtin_amdgcn_perm(nf, nf, 0x0c030c02u);
+                        unsigned long long X = (unsigned long long)x1 << 32 | x0, X4, X2;
+                        asm("v_lshlrev_b64 %0, 4, %1" : "=v"(X4) : "v"(X));
+                        const uint32_t y0 = (x0 | (uint32_t)X4) & m0f, y1 = (x1 | (uint32_t)(X4 >> 32)) & m0f;
+                        X = (unsigned long long)y1 << 32 | y0;
+                        asm("v_lshlrev_b64 %0, 2, %1" : "=v"(X2) : "v"(X));
+                        const uint32_t n0 = (y0 | (uint32_t)X2) & m33, n1 = (y1 | (uint32_t)(X2 >> 32)) & m33;
                         uint32_t n05, n15;
                         asm("v_lshl_or_b32 %0, %1, 2, %1" : "=v"(n05) : "v"(n0));
                         asm("v_lshl_or_b32 %0, %1, 2, %1" : "=v"(n15) : "v"(n1));
@@ -2338,8 +2365,9 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
             const int k = i / (ncyc * 5), j = i - k * ncyc * 5;
             const int c = j / 5, slot = j - c * 5;  // slots A C T G N
             const uint32_t* hk = hist + k * 32;
-            const unsigned long long kept = *reinterpret_cast<const unsigned long long*>(hk + rcell(c, slot < 4 ? 4 + slot : kRNSlot + 4));
-            const unsigned long long rem = *reinterpret_cast<const unsigned long long*>(hk + rcell(c, slot < 4 ? slot : kRNSlot));
+            const int rs = slot < 4 ? rem_slot(PAIRED ? k : 0, slot) : kRNSlot;  // (read 2's rows: relabelled)
+            const unsigned long long kept = *reinterpret_cast<const unsigned long long*>(hk + rcell(c, rs + 4));
+            const unsigned long long rem = *reinterpret_cast<const unsigned long long*>(hk + rcell(c, rs));
             const int cls = slot_class(slot);
             const unsigned long long vals[2] = {kept + rem, kept};
 #pragma unroll
