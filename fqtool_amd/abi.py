@@ -160,6 +160,16 @@ class FqRawWindow(ctypes.Structure):  # fq_raw_window
     _fields_ = [("bytes", ctypes.c_void_p * 2), ("n", ctypes.c_uint64 * 2)]
 
 
+FQ_RAW_BGZF_MEMBERS = 8192
+FQ_RAW_STOP_INFLATE = 2
+
+
+class FqRawBgzfWindow(ctypes.Structure):  # fq_raw_bgzf_window
+    _fields_ = [("comp", ctypes.c_void_p * 2), ("comp_bytes", ctypes.c_uint64 * 2),
+                ("m", ctypes.POINTER(FqInflateMember) * 2), ("members", ctypes.c_uint32 * 2),
+                ("skip", ctypes.c_uint32 * 2), ("n", ctypes.c_uint64 * 2)]
+
+
 class FqRawResult(ctypes.Structure):  # fq_raw_result
     _fields_ = [("pairs", ctypes.c_int32), ("stop", ctypes.c_int32), ("max_len", ctypes.c_int32),
                 ("pad", ctypes.c_int32), ("carry", ctypes.c_uint64 * 2), ("text_bytes", ctypes.c_uint64 * 2)]
@@ -303,6 +313,7 @@ def load_engine(path=ENGINE_LIB):
     lib.fq_engine_pending.argtypes = [vp]
     lib.fq_engine_raw_begin.argtypes = [vp, u64, u64]
     lib.fq_engine_raw_enqueue.argtypes = [vp, ctypes.POINTER(FqRawWindow)]
+    lib.fq_engine_raw_enqueue_bgzf.argtypes = [vp, ctypes.POINTER(FqRawBgzfWindow)]
     lib.fq_engine_raw_launch.argtypes = [vp, ctypes.POINTER(FqRawResult), ctypes.POINTER(FqRawOut), u64]
     lib.fq_engine_raw_wait.argtypes = [vp, ctypes.POINTER(FqRawResult)]
     lib.fq_engine_raw_end.argtypes = [vp]
@@ -379,7 +390,7 @@ ENGINE_SYMBOLS = [
     "fq_engine_last_kernel_ms", "fq_engine_submit", "fq_engine_submit_text", "fq_engine_poll", "fq_engine_pending", "fq_host_alloc",
     "fq_host_free", "fq_dup_create", "fq_dup_destroy", "fq_dup_reset", "fq_engine_set_dup", "fq_dup_merge",
     "fq_dup_stat", "fq_kmer_open", "fq_kmer_close", "fq_kmer_count", "fq_kmer_find",
-    "fq_engine_raw_begin", "fq_engine_raw_enqueue", "fq_engine_raw_launch", "fq_engine_raw_wait", "fq_engine_raw_end", "fq_host_register", "fq_host_unregister",
+    "fq_engine_raw_begin", "fq_engine_raw_enqueue", "fq_engine_raw_enqueue_bgzf", "fq_engine_raw_launch", "fq_engine_raw_wait", "fq_engine_raw_end", "fq_host_register", "fq_host_unregister",
     "fq_deflate_bound", "fq_deflate_code_lengths", "fq_deflate_create", "fq_deflate_destroy", "fq_deflate_bgzf",
     "fq_engine_set_gz_out", "fq_egress_bound", "fq_engine_set_egress", "fq_engine_submit_text_routed", "fq_engine_raw_launch_routed",
     "fq_engine_set_umi", "fq_egress_bound_umi",

@@ -77,6 +77,15 @@ struct Slot {
     hipEvent_t ev_idx = nullptr;
     fq_raw_out* raw_out = nullptr;  // the pending raw pack's output descriptor
     uint64_t raw_n[2] = {0, 0};     // the window's raw bytes
+    // BGZF windows (fq_engine_raw_enqueue_bgzf; made at the first one): each mate's compressed bytes,
+    // the members' table (pinned copy and device copy), the claim counter and bad-member counts
+    uint8_t* d_bcomp[2] = {nullptr, nullptr};
+    size_t bcomp_cap[2] = {0, 0};
+    fq_raw_bgzf_desc* h_bdesc = nullptr;  // pinned [2 * FQ_RAW_BGZF_MEMBERS]
+    fq_raw_bgzf_desc* d_bdesc = nullptr;
+    uint32_t* d_bctl = nullptr;           // [4]
+    hipEvent_t ev_b0 = nullptr, ev_b1 = nullptr;  // FQ_ENGINE_TIMING: around the inflate
+    bool b_timed = false;
     int* d_err = nullptr;  // this pack's device error word (cleared at submit, set by its kernels)
     int* h_err = nullptr;  // pinned: d_err as of this pack's kernels
     bool busy = false;      // events recorded and not yet waited for
@@ -261,6 +270,13 @@ static void free_slot(Slot& s) {
     if (s.d_rstate) (void)hipFree(s.d_rstate);
     if (s.h_rstate) (void)hipHostFree(s.h_rstate);
     if (s.ev_idx) (void)hipEventDestroy(s.ev_idx);
+    for (int m = 0; m < 2; ++m)
+        if (s.d_bcomp[m]) (void)hipFree(s.d_bcomp[m]);
+    if (s.h_bdesc) (void)hipHostFree(s.h_bdesc);
+    if (s.d_bdesc) (void)hipFree(s.d_bdesc);
+    if (s.d_bctl) (void)hipFree(s.d_bctl);
+    if (s.ev_b0) (void)hipEventDestroy(s.ev_b0);
+    if (s.ev_b1) (void)hipEventDestroy(s.ev_b1);
     if (s.d_err) (void)hipFree(s.d_err);
     if (s.h_err) (void)hipHostFree(s.h_err);
     if (s.ev_in) (void)hipEventDestroy(s.ev_in);
@@ -1294,6 +1310,8 @@ int fq_engine_raw_begin(fq_engine* e, uint64_t window_cap, uint64_t carry_cap) {
     return FQ_OK;
 }
 
+static int raw_index(fq_engine* e, int k, const uint64_t* n, const uint32_t* d_infl_bad);
+
 int fq_engine_raw_enqueue(fq_engine* e, const fq_raw_window* w) {
     if (!e || !w) return FQ_E_INVALID;
     if (!e->raw) return fail(e, FQ_E_INVALID, "fq_engine_raw_enqueue before fq_engine_raw_begin");
@@ -1322,14 +1340,22 @@ int fq_engine_raw_enqueue(fq_engine* e, const fq_raw_window* w) {
         lc.in = s.ev_in, lc.in_owner = e;
     }
     HIP_TRY(e, hipStreamWaitEvent(e->s_idx, s.ev_in, 0));
-    s.raw_n[0] = w->n[0];
-    s.raw_n[1] = pe ? w->n[1] : 0;
+    s.b_timed = false;
+    return raw_index(e, k, w->n, nullptr);
+}
+
+// the index of slot k's window of n[m] bytes on the index stream, and the window enqueued
+static int raw_index(fq_engine* e, int k, const uint64_t* n, const uint32_t* d_infl_bad) {
+    Slot& s = e->slots[k];
+    const bool pe = e->p.paired;
+    s.raw_n[0] = n[0];
+    s.raw_n[1] = pe ? n[1] : 0;
     fq_raw_text_args a{};
     const Slot* ps = e->raw_prev_slot >= 0 ? &e->slots[e->raw_prev_slot] : nullptr;
     for (int m = 0; m < 2; ++m) {
         a.text[m] = s.d_text[m];
         a.prev_text[m] = ps ? ps->d_text[m] : nullptr;
-        a.raw_bytes[m] = (uint32_t)w->n[m];
+        a.raw_bytes[m] = (uint32_t)s.raw_n[m];
         a.bcnt[m] = s.d_bcnt[m];
         a.bbase[m] = s.d_bbase[m];
         a.lines[m] = s.d_lines[m];
@@ -1337,6 +1363,7 @@ int fq_engine_raw_enqueue(fq_engine* e, const fq_raw_window* w) {
     }
     a.prev_state = ps ? ps->d_rstate : nullptr;
     a.state = s.d_rstate;
+    a.infl_bad = d_infl_bad;
     a.carry_cap = (uint32_t)e->raw_ccap;
     a.nblocks = e->raw_nblocks;
     a.cap_lines = (uint32_t)(4 * ((size_t)e->max_batch + 1) + 8);
@@ -1348,6 +1375,125 @@ int fq_engine_raw_enqueue(fq_engine* e, const fq_raw_window* w) {
     e->raw_queued.push_back(k);
     e->raw_prev_slot = k;
     return FQ_OK;
+}
+
+// the BGZF-window buffers of slot s: the members' table, and room for comp[m] bytes of each mate
+static int ensure_bgzf(fq_engine* e, Slot& s, const uint64_t* comp) {
+    if (!s.d_bdesc) {
+        const size_t tab = (size_t)2 * FQ_RAW_BGZF_MEMBERS * sizeof(fq_raw_bgzf_desc);
+        HIP_TRY(e, fq_inflate_spans_prepare());
+        HIP_TRY(e, hipHostMalloc((void**)&s.h_bdesc, tab, hipHostMallocDefault));
+        HIP_TRY(e, hipMalloc(&s.d_bdesc, tab));
+        HIP_TRY(e, hipMalloc(&s.d_bctl, 4 * sizeof(uint32_t)));
+        if (engine_timing()) {
+            HIP_TRY(e, hipEventCreate(&s.ev_b0));
+            HIP_TRY(e, hipEventCreate(&s.ev_b1));
+        }
+    }
+    for (int m = 0; m < (e->p.paired ? 2 : 1); ++m) {
+        if (comp[m] <= s.bcomp_cap[m]) continue;
+        // (grown with some room, never beyond the window capacity, which bounds comp[m])
+        const size_t cap = (size_t)std::min<uint64_t>(e->raw_wcap, std::max<uint64_t>(comp[m] + comp[m] / 4, 1u << 20));
+        if (s.d_bcomp[m]) (void)hipFree(s.d_bcomp[m]);
+        s.d_bcomp[m] = nullptr;
+        s.bcomp_cap[m] = 0;
+        HIP_TRY(e, hipMalloc(&s.d_bcomp[m], std::max<size_t>(cap, 16)));
+        s.bcomp_cap[m] = cap;
+    }
+    return FQ_OK;
+}
+
+// FQ_BGZF_CLAIM=len (profiling): the members are claimed largest payload first, not in stream order
+static bool bgzf_claim_by_len() {
+    static const bool on = [] {
+        const char* v = std::getenv("FQ_BGZF_CLAIM");
+        return v && std::strcmp(v, "len") == 0;
+    }();
+    return on;
+}
+
+int fq_engine_raw_enqueue_bgzf(fq_engine* e, const fq_raw_bgzf_window* w) {
+    if (!e || !w) return FQ_E_INVALID;
+    if (!e->raw) return fail(e, FQ_E_INVALID, "fq_engine_raw_enqueue_bgzf before fq_engine_raw_begin");
+    if (e->raw_queued.size() >= 3) return fail(e, FQ_E_INVALID, "three raw windows are already waiting for fq_engine_raw_launch");
+    const bool pe = e->p.paired;
+    const int mates = pe ? 2 : 1;
+    if (e->raw_ccap < 65536) return fail(e, FQ_E_INVALID, "BGZF windows need a carry capacity of at least 65536 bytes");
+    uint64_t n[2] = {0, 0}, comp[2] = {0, 0};
+    for (int m = 0; m < mates; ++m) {
+        if (w->members[m] > FQ_RAW_BGZF_MEMBERS) return fail(e, FQ_E_INVALID, "BGZF window: too many members");
+        if (w->comp_bytes[m] > e->raw_wcap || (w->comp_bytes[m] && !w->comp[m]) || (w->members[m] && !w->m[m]))
+            return fail(e, FQ_E_INVALID, "BGZF window: compressed bytes exceed the window capacity");
+        if (w->skip[m] > e->raw_ccap) return fail(e, FQ_E_INVALID, "BGZF window: skip exceeds the carry capacity");
+        uint64_t total = 0;
+        for (uint32_t i = 0; i < w->members[m]; ++i) {
+            const fq_inflate_member& mb = w->m[m][i];
+            if (mb.in_len > FQ_INFLATE_MAX || mb.isize > FQ_INFLATE_MAX) return fail(e, FQ_E_INVALID, "BGZF window: member exceeds FQ_INFLATE_MAX");
+            if (mb.in_off > w->comp_bytes[m] || mb.in_len > w->comp_bytes[m] - mb.in_off)
+                return fail(e, FQ_E_INVALID, "BGZF window: a payload lies outside the compressed bytes");
+            total += mb.isize;
+        }
+        if (w->n[m] > e->raw_wcap || total < (uint64_t)w->skip[m] + w->n[m] || total - w->skip[m] > e->raw_wcap)
+            return fail(e, FQ_E_INVALID, "BGZF window: the members do not match skip and n, or exceed the window capacity");
+        n[m] = w->n[m];
+        comp[m] = w->comp_bytes[m];
+    }
+    HIP_TRY(e, hipSetDevice(e->device));
+    const int k = (e->raw_prev_slot + 1) % kRawSlots;
+    int rc = retire_slot(e, k);
+    if (rc != FQ_OK) return rc;
+    Slot& s = e->slots[k];
+    if ((rc = alloc_slot(e, s)) != FQ_OK) return rc;
+    if ((rc = ensure_raw(e, s)) != FQ_OK) return rc;
+    if ((rc = ensure_bgzf(e, s, comp)) != FQ_OK) return rc;
+    // the table in claim order: the mates interleaved in stream order (each mate's members in the
+    // proportion of its count), so that both mates' outputs fill at the same rate
+    uint32_t nd = 0;
+    {
+        uint32_t at[2] = {0, 0}, off[2] = {0, 0};
+        const uint32_t c0 = w->members[0], c1 = pe ? w->members[1] : 0;
+        while (at[0] < c0 || at[1] < c1) {
+            // mate 1 goes next while it is behind mate 0 in its share of the members
+            const int m = at[1] < c1 && (at[0] >= c0 || (uint64_t)at[1] * c0 < (uint64_t)at[0] * c1) ? 1 : 0;
+            const fq_inflate_member& mb = w->m[m][at[m]++];
+            fq_raw_bgzf_desc& d = s.h_bdesc[nd++];
+            d.in_off = (uint32_t)mb.in_off;
+            d.in_len = mb.in_len;
+            d.isize = mb.isize;
+            d.crc = mb.crc;
+            d.out_off = off[m];
+            d.mate = (uint32_t)m;
+            d.pad[0] = d.pad[1] = 0;
+            off[m] += mb.isize;
+        }
+        if (bgzf_claim_by_len())
+            std::stable_sort(s.h_bdesc, s.h_bdesc + nd, [](const fq_raw_bgzf_desc& x, const fq_raw_bgzf_desc& y) { return x.in_len > y.in_len; });
+    }
+    {
+        LinkChain& lc = link_chain(e->device);
+        std::lock_guard<std::mutex> g(lc.m);
+        if (lc.in && lc.in_owner != e) HIP_TRY(e, hipStreamWaitEvent(e->s_in, lc.in, 0));
+        for (int m = 0; m < mates; ++m)
+            if (comp[m]) HIP_TRY(e, hipMemcpyAsync(s.d_bcomp[m], w->comp[m], comp[m], hipMemcpyHostToDevice, e->s_in));
+        if (nd) HIP_TRY(e, hipMemcpyAsync(s.d_bdesc, s.h_bdesc, (size_t)nd * sizeof(fq_raw_bgzf_desc), hipMemcpyHostToDevice, e->s_in));
+        HIP_TRY(e, hipEventRecord(s.ev_in, e->s_in));
+        lc.in = s.ev_in, lc.in_owner = e;
+    }
+    HIP_TRY(e, hipStreamWaitEvent(e->s_idx, s.ev_in, 0));
+    HIP_TRY(e, hipMemsetAsync(s.d_bctl, 0, 4 * sizeof(uint32_t), e->s_idx));
+    fq_inflate_spans a{};
+    for (int m = 0; m < mates; ++m) {
+        a.comp[m] = s.d_bcomp[m];
+        a.out[m] = reinterpret_cast<uint8_t*>(s.d_text[m]) + e->raw_ccap - w->skip[m];
+    }
+    a.desc = s.d_bdesc;
+    a.n = nd;
+    a.ctl = s.d_bctl;
+    s.b_timed = s.ev_b0 != nullptr;
+    if (s.b_timed) HIP_TRY(e, hipEventRecord(s.ev_b0, e->s_idx));
+    HIP_TRY(e, fq_launch_inflate_spans(a, e->cus, e->s_idx));
+    if (s.b_timed) HIP_TRY(e, hipEventRecord(s.ev_b1, e->s_idx));
+    return raw_index(e, k, n, s.d_bctl + 1);
 }
 
 // the oldest enqueued window's index, once its copy back has landed
@@ -1364,15 +1510,28 @@ static void raw_result_of(const fq_engine* e, const Slot& s, fq_raw_result* r) {
         r->max_len = std::max(r->max_len, st.max_len);
         if (st.overflow || st.first_bad == n) r->stop = 1;
     }
+    for (int m = 0; m < mates; ++m)
+        if (s.h_rstate[m].infl_bad) r->stop = FQ_RAW_STOP_INFLATE;
+}
+
+// FQ_ENGINE_TIMING: an indexed BGZF window's inflate, by the events around its launch (once)
+static void report_inflate(Slot& s) {
+    if (!s.b_timed) return;
+    s.b_timed = false;
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, s.ev_b0, s.ev_b1) == hipSuccess)
+        std::fprintf(stderr, "fq_engine_raw: BGZF window of %llu + %llu bytes inflated in %.3f ms\n", (unsigned long long)s.raw_n[0],
+                     (unsigned long long)s.raw_n[1], (double)ms);
 }
 
 int fq_engine_raw_wait(fq_engine* e, fq_raw_result* r) {
     if (!e) return FQ_E_INVALID;
     if (e->raw_queued.empty()) return fail(e, FQ_E_INVALID, "fq_engine_raw_wait without an enqueued window");
     HIP_TRY(e, hipSetDevice(e->device));
-    const Slot& s = e->slots[e->raw_queued.front()];
+    Slot& s = e->slots[e->raw_queued.front()];
     HIP_TRY(e, hipEventSynchronize(s.ev_idx));
     if (r) raw_result_of(e, s, r);
+    report_inflate(s);
     return FQ_OK;
 }
 
@@ -1389,6 +1548,7 @@ int fq_engine_raw_launch(fq_engine* e, fq_raw_result* r, fq_raw_out* out, uint64
     const int k = e->raw_queued.front();
     Slot& s = e->slots[k];
     HIP_TRY(e, hipEventSynchronize(s.ev_idx));  // (returns at once after fq_engine_raw_wait)
+    report_inflate(s);
     const bool pe = e->p.paired;
     const int mates = pe ? 2 : 1;
     raw_result_of(e, s, r);
@@ -1497,6 +1657,7 @@ int fq_engine_raw_launch_routed(fq_engine* e, fq_raw_result* r, fq_raw_egress_ou
     const int k = e->raw_queued.front();
     Slot& s = e->slots[k];
     HIP_TRY(e, hipEventSynchronize(s.ev_idx));  // (returns at once after fq_engine_raw_wait)
+    report_inflate(s);
     const bool pe = e->p.paired;
     const int mates = pe ? 2 : 1;
     raw_result_of(e, s, r);

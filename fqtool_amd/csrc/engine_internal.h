@@ -154,7 +154,8 @@ struct fq_raw_state {
     uint32_t total_lines;
     uint32_t consumed;    // text bytes taken by the pack's records
     int32_t n;            // records (pairs) of the pack
-    uint32_t pad[2];
+    uint32_t infl_bad;    // members of this or an earlier BGZF window that did not inflate (overflow is set)
+    uint32_t pad;
 };
 struct fq_raw_text_args {
     char* text[2];
@@ -162,6 +163,7 @@ struct fq_raw_text_args {
     const fq_raw_state* prev_state;  // previous window's states, nullptr at the start of the stream
     fq_raw_state* state;             // [2]
     uint32_t raw_bytes[2];
+    const uint32_t* infl_bad;        // [2]: a BGZF window's members that did not inflate, nullptr for a plain window
     uint32_t carry_cap;              // the raw bytes land at this buffer offset
     uint32_t nblocks;                // 4 KiB blocks of the buffer
     uint32_t* bcnt[2];
@@ -175,6 +177,27 @@ struct fq_raw_text_args {
 size_t fq_raw_scan_temp_bytes(int nblocks, int n);
 hipError_t fq_launch_raw_index(const fq_raw_text_args& a, int mates, int cap_batch, void* d_temp, size_t temp_bytes,
                                hipStream_t s);
+// BGZF windows of the raw stream (inflate.hip): one launch inflates both mates' members.  The table
+// is in claim order: the waves take its entries one after another from ctl[0], and count the members
+// of mate m that are not FQ_INFL_OK in ctl[1 + m] (all three cleared on the stream before the launch).
+struct fq_raw_bgzf_desc {
+    uint32_t in_off;   // the payload's offset in comp[mate]
+    uint32_t in_len;
+    uint32_t isize;
+    uint32_t crc;
+    uint32_t out_off;  // the member's offset in out[mate]
+    uint32_t mate;
+    uint32_t pad[2];
+};
+struct fq_inflate_spans {
+    const uint8_t* comp[2];
+    uint8_t* out[2];
+    const fq_raw_bgzf_desc* desc;
+    uint32_t n;
+    uint32_t* ctl;  // [3]
+};
+hipError_t fq_inflate_spans_prepare();
+hipError_t fq_launch_inflate_spans(const fq_inflate_spans& a, int cus, hipStream_t s);
 // trimmed-adapter entries of mate m appended to its output text (at *d_text_total, within cap bytes
 // of d_out; *d_total = the entries' bytes, ~0 if they would not fit)
 hipError_t fq_launch_raw_adapters(const char* d_text, const fq_text_rec* d_rec, const fq_read_result* d_res, int n,

@@ -1,7 +1,7 @@
 // inflate.hip -- BGZF members inflated on the device (include/fqengine.h, "device inflate").
 //
 // fq_inflate_kernel: one wave64 per workgroup, one member per wave at a time (inflate_core.h has
-// the routine); the grid is four workgroups per CU (the output window lives in LDS, ~38 KiB a
+// the routine); fq_inflate_spans_kernel is the same for the raw stream's BGZF windows.  The grid is four workgroups per CU (the output window lives in LDS, ~38 KiB a
 // wave) and strides over the members.  The host side validates every descriptor before anything
 // is copied or launched, so the kernel sees only payloads inside the compressed buffer and output
 // ranges inside the output buffer; what the payload bytes say is the kernel's to survive.
@@ -34,6 +34,39 @@ __global__ __launch_bounds__(64) void fq_inflate_kernel(const uint8_t* comp, fq_
             m[i].produced = produced;
         }
     }
+}
+
+// The raw stream's BGZF windows: the members of both mates in one table, claimed in table order from
+// a device counter (lane 0 takes the next index and broadcasts it), so the two mates share one grid
+// and one tail.  Same LDS and registers per wave as fq_inflate_kernel.
+__global__ __launch_bounds__(64) void fq_inflate_spans_kernel(fq_inflate_spans a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t fq_infl_lds[];
+    for (;;) {
+        uint32_t i = 0;
+        if (threadIdx.x == 0) i = atomicAdd(&a.ctl[0], 1u);
+        i = fq_uni(i);
+        if (i >= a.n) break;
+        const fq_raw_bgzf_desc d = a.desc[i];
+        const uint32_t mate = fq_uni(d.mate) & 1u;
+        // (the host checked the limits; clamped again so that no descriptor can widen an access)
+        const uint32_t in_len = std::min<uint32_t>(fq_uni(d.in_len), FQ_INFLATE_MAX);
+        const uint32_t isize = std::min<uint32_t>(fq_uni(d.isize), FQ_INFLATE_MAX);
+        uint32_t produced = 0;
+        const uint32_t st = fq_inflate_one(fq_infl_lds, a.comp[mate] + fq_uni(d.in_off), in_len, isize, fq_uni(d.crc),
+                                           a.out[mate] + fq_uni(d.out_off), produced);
+        if (st != FQ_IS_OK && threadIdx.x == 0) atomicAdd(&a.ctl[1 + mate], 1u);
+    }
+}
+
+hipError_t fq_inflate_spans_prepare() {
+    return hipFuncSetAttribute((const void*)fq_inflate_spans_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FQ_IL_TOTAL);
+}
+
+hipError_t fq_launch_inflate_spans(const fq_inflate_spans& a, int cus, hipStream_t s) {
+    if (a.n == 0) return hipSuccess;
+    const int grid = (int)std::min<size_t>(a.n, (size_t)4 * std::max(1, cus));
+    hipLaunchKernelGGL(fq_inflate_spans_kernel, dim3(grid), dim3(64), FQ_IL_TOTAL, s, a);
+    return hipGetLastError();
 }
 
 struct fq_inflate {

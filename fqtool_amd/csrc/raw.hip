@@ -55,7 +55,9 @@ __global__ void raw_carry_kernel(fq_raw_text_args a) {
     const int m = blockIdx.y;
     const fq_raw_state* ps = a.prev_state ? a.prev_state + m : nullptr;
     uint32_t carry = ps ? ps->avail - ps->consumed : 0u;
-    const bool over = carry > a.carry_cap || (ps && ps->overflow);
+    // (a BGZF window with a member that did not inflate is taken as an overflow: none of it is read)
+    const uint32_t bad = (a.infl_bad ? a.infl_bad[m] : 0u) + (ps ? ps->infl_bad : 0u);
+    const bool over = carry > a.carry_cap || (ps && ps->overflow) || bad;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         // (an overflow indexes nothing: the host resumes before the carried bytes)
         fq_raw_state& s = a.state[m];
@@ -63,6 +65,7 @@ __global__ void raw_carry_kernel(fq_raw_text_args a) {
         s.carry_in = carry;
         s.avail = over ? 0u : carry + a.raw_bytes[m];
         s.overflow = over ? 1u : 0u;
+        s.infl_bad = bad;
         s.first_bad = INT_MAX;
         s.complete = 0;
         s.max_len = 0;

@@ -389,6 +389,13 @@ class BgzfSource {
         }
         return true;
     }
+    // the member chain, for the raw stream's window planner (bgzf_plan.h)
+    void chain(std::vector<BgzfChainMember>& out) const {
+        out.clear();
+        out.reserve(members_.size());
+        for (const Member& m : members_) out.push_back(BgzfChainMember{(uint64_t)m.data, (uint32_t)m.clen, m.isize, m.crc});
+    }
+    bool device_fits() const { return device_fits_; }
     ~BgzfSource() {
         if (ahead_.valid()) ahead_.wait();
         // (FQ_TIMING keeps the tool's teardown, so this is reached; no batch is inflating any more)
@@ -816,6 +823,13 @@ int gz_inflate_threads() {
 }
 
 bool is_bgzf_chain(const std::string& path) { return BgzfSource::open(path, 1) != nullptr; }
+bool bgzf_chain_members(const std::string& path, std::vector<BgzfChainMember>& out, bool* fits) {
+    const std::unique_ptr<BgzfSource> b = BgzfSource::open(path, 1);
+    if (!b) return false;
+    b->chain(out);
+    if (fits) *fits = b->device_fits();
+    return true;
+}
 
 // ---- FqBulkReader ----
 FqBulkReader::FqBulkReader(const std::string& path, bool phred64, int buf_size, int gz_device)

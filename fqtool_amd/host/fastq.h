@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/fqengine.h"
+#include "bgzf_plan.h"
 
 
 namespace fqhost {
@@ -162,6 +163,8 @@ int gz_inflate_threads();
 // the file is a chain of BGZF members from its first byte to its last (the bulk reader then
 // inflates it member by member; only the headers are looked at here)
 bool is_bgzf_chain(const std::string& path);
+// the same, and the chain's members (bgzf_plan.h); *fits = no member above FQ_INFLATE_MAX
+bool bgzf_chain_members(const std::string& path, std::vector<BgzfChainMember>& out, bool* fits);
 
 class FqBulkReader {
    public:

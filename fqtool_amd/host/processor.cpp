@@ -61,6 +61,8 @@
 #pragma weak fq_ora_words
 #pragma weak fq_ora_read
 #pragma weak fq_engine_set_ora
+// BGZF windows of the raw stream (FQ_GZ_IN_DEVICE=2): without the call BGZF inputs keep their route
+#pragma weak fq_engine_raw_enqueue_bgzf
 
 namespace fqhost {
 namespace {
@@ -1710,6 +1712,19 @@ struct Lane {
     double raw_turn_wait_s = 0, raw_idx_wait_s = 0;  // several engines: waiting for the turn, for the own index
     std::string raw_end;                    // why it ended
     std::unique_ptr<ParGzSource> pre_gz[2];  // gzip inputs' inflaters, started ahead of the engines
+    // BGZF inputs inflated on the device (FQ_GZ_IN_DEVICE=2): each mate's window planner, set by
+    // run_tool when the route applies, and the members its windows sent
+    std::unique_ptr<BgzfPlanner> bgzf[2];
+    uint64_t bgzf_members[2] = {0, 0};
+
+    // a raw window's capacity: up to 48 MiB per mate (a pack of `target` 2x150 pairs is ~45 MiB; longer
+    // reads make smaller packs; smaller packs, --pack_pairs: windows of ~1.3 packs of the estimated
+    // record size, so the page-locked stages shrink with them)
+    static uint64_t raw_window_cap(int target, int est_len) {
+        const uint64_t rec_est = 2 * (uint64_t)std::max(est_len, 16) + 72;
+        const uint64_t wfit = ((uint64_t)(1.3 * (double)target * (double)rec_est) + ((uint64_t)1 << 20)) & ~(((uint64_t)1 << 20) - 1);
+        return std::min<uint64_t>((uint64_t)48 << 20, std::max<uint64_t>((uint64_t)4 << 20, wfit));
+    }
 
     RawResume run_raw(const std::string* files, int mates, int target, int est_len, Queue<std::unique_ptr<Pack>>& spare, Pool& pool) {
         RawResume rr;
@@ -1728,7 +1743,10 @@ struct Lane {
         // then resumes there and meets the failure as the reference's reader does.
         std::unique_ptr<ParGzSource> gzs[2];
         std::atomic<bool> src_failed{false};
-        const bool gz_in = ends_with_gz(files[0]);
+        // BGZF inputs on the device: the windows' compressed bytes are read with pread like a plain
+        // file's, the stream's size is the chain's inflated size
+        const bool bgzf_in = bgzf[0] != nullptr;
+        const bool gz_in = ends_with_gz(files[0]) && !bgzf_in;
         for (int m = 0; m < mates; ++m) {
             if (gz_in) {
                 // (opened, and inflating, before the engines were made: run_tool)
@@ -1743,7 +1761,7 @@ struct Lane {
                 close_all();
                 return rr;  // (the host reader takes the whole input)
             }
-            size[m] = (uint64_t)st.st_size;
+            size[m] = bgzf_in ? bgzf[m]->size() : (uint64_t)st.st_size;
             (void)posix_fadvise(fd[m], 0, 0, POSIX_FADV_SEQUENTIAL);
         }
         // windows of up to 48 MiB per mate (a pack of `target` 2x150 pairs is ~45 MiB; longer reads
@@ -1752,16 +1770,15 @@ struct Lane {
         // carry (partial records, the mates' imbalance); six windows in the engine at once
         // (smaller packs, --pack_pairs: windows of ~1.3 packs of the estimated record size, so the
         // page-locked stages shrink with them)
-        const uint64_t rec_est = 2 * (uint64_t)std::max(est_len, 16) + 72;
-        const uint64_t wfit = ((uint64_t)(1.3 * (double)target * (double)rec_est) + ((uint64_t)1 << 20)) & ~(((uint64_t)1 << 20) - 1);
-        const uint64_t wcap = std::min<uint64_t>((uint64_t)48 << 20, std::max<uint64_t>((uint64_t)4 << 20, wfit));
+        const uint64_t wcap = raw_window_cap(target, est_len);
         const uint64_t ccap = (uint64_t)16 << 20;
         // records-only egress (FQ_RAW_EGRESS=host): the engine sends back records and line offsets,
         // the formatter writes the output from the staging window, which then keeps the carry
         // capacity free in front of the window bytes (the device buffer's layout)
         const char* eg_env = std::getenv("FQ_RAW_EGRESS");
         // (not with --phred64 on the device: the host windows are never converted; nor with split outputs)
-        const bool recs = !merge && !gz_level && !routed && !phred64_dev && !cut_every && eg_env && std::string(eg_env) == "host";
+        // (nor on BGZF windows: the stage holds no text)
+        const bool recs = !bgzf_in && !merge && !gz_level && !routed && !phred64_dev && !cut_every && eg_env && std::string(eg_env) == "host";
         const uint64_t off0 = recs ? ccap : 0;
         const int raw_depth = 4;  // packs launched and not yet polled
         const size_t raw_ahead = 3;  // windows enqueued ahead of their launch (the copy-in queue)
@@ -1801,6 +1818,7 @@ struct Lane {
             uint64_t start[2] = {0, 0}, n[2] = {0, 0};
             int stage = -1;
             uint64_t id = 0;
+            BgzfWindowPlan bz[2];  // (BGZF inputs: the window's members; the stage holds their payloads)
         };
         // published by this thread after each launch, read by the window reader
         std::mutex fb_m;
@@ -1813,7 +1831,7 @@ struct Lane {
         const uint64_t piece_bytes = (uint64_t)(pc_env ? std::max(1, atoi(pc_env)) : 1) << 20;
         const char* cp_env = std::getenv("FQ_RAW_COPY");
         const char* mp[2] = {nullptr, nullptr};
-        if (cp_env && std::string(cp_env) == "mmap")
+        if (cp_env && std::string(cp_env) == "mmap" && !bgzf_in)
             for (int m = 0; m < mates; ++m) {
                 void* a = mmap(nullptr, (size_t)size[m], PROT_READ, MAP_PRIVATE, fd[m], 0);
                 if (a != MAP_FAILED) {
@@ -1860,8 +1878,19 @@ struct Lane {
                             want = need <= 0 ? 0 : (uint64_t)need;
                         }
                         w.start[m] = pos[m];
-                        w.n[m] = std::min(std::min<uint64_t>((want + 4095) / 4096 * 4096, wcap), rsize[m] - pos[m]);
+                        if (bgzf_in) {  // whole gzread calls of the stream (bgzf_plan.h)
+                            if (!bgzf[m]->next(pos[m], want, w.bz[m])) throw std::runtime_error("BGZF window planner: no window fits");
+                            w.n[m] = w.bz[m].n;
+                        } else {
+                            w.n[m] = std::min(std::min<uint64_t>((want + 4095) / 4096 * 4096, wcap), rsize[m] - pos[m]);
+                        }
                         pos[m] += w.n[m];
+                    }
+                    // what is read into the stage: the window's bytes, or its members' payloads
+                    uint64_t src_off[2], src_len[2];
+                    for (int m = 0; m < 2; ++m) {
+                        src_off[m] = bgzf_in ? w.bz[m].comp_off : w.start[m];
+                        src_len[m] = bgzf_in ? w.bz[m].comp_bytes : w.n[m];
                     }
                     const auto s0 = std::chrono::steady_clock::now();
                     if (!free_stages.pop(w.stage)) break;
@@ -1871,8 +1900,8 @@ struct Lane {
                     const uint64_t piece = piece_bytes;
                     int pieces[2] = {0, 0};
                     for (int m = 0; m < mates; ++m) {
-                        st.buf[m].resize_uninit((size_t)(off0 + std::max<uint64_t>(w.n[m], 1)));
-                        pieces[m] = (int)((w.n[m] + piece - 1) / piece);
+                        st.buf[m].resize_uninit((size_t)(off0 + std::max<uint64_t>(src_len[m], 1)));
+                        pieces[m] = (int)((src_len[m] + piece - 1) / piece);
                     }
                     std::atomic<bool> short_read{false};
                     if (gz_in) {
@@ -1904,7 +1933,7 @@ struct Lane {
                     pool.run(pieces[0] + pieces[1], [&](int k) {
                         const int m = k < pieces[0] ? 0 : 1;
                         const uint64_t o = (uint64_t)(m ? k - pieces[0] : k) * piece;
-                        const uint64_t len = std::min(piece, w.n[m] - o);
+                        const uint64_t len = std::min(piece, src_len[m] - o);
                         char* dst = st.buf[m].data() + off0 + o;
                         if (mp[m]) {  // (FQ_RAW_COPY=mmap: copy from a read-only mapping)
                             std::memcpy(dst, mp[m] + w.start[m] + o, (size_t)len);
@@ -1912,7 +1941,7 @@ struct Lane {
                         }
                         uint64_t got = 0;
                         while (got < len) {
-                            const ssize_t r = pread(fd[m], dst + got, (size_t)(len - got), (off_t)(w.start[m] + o + got));
+                            const ssize_t r = pread(fd[m], dst + got, (size_t)(len - got), (off_t)(src_off[m] + o + got));
                             if (r <= 0) {
                                 short_read = true;
                                 return;
@@ -1933,7 +1962,40 @@ struct Lane {
         });
         std::deque<Win> wins;  // enqueued, not launched
         bool input_done = false;
+        std::vector<fq_inflate_member> bz_desc[2];
+        auto enqueue_bgzf_window = [&](const Win& w) {  // the window's members from its stage
+            fq_raw_bgzf_window bw{};
+            for (int m = 0; m < mates; ++m) {
+                const BgzfWindowPlan& b = w.bz[m];
+                const std::vector<BgzfChainMember>& ms = bgzf[m]->members();
+                bz_desc[m].resize(b.end - b.first);
+                for (size_t i = b.first; i < b.end; ++i) {
+                    fq_inflate_member& d = bz_desc[m][i - b.first];
+                    std::memset(&d, 0, sizeof d);
+                    d.in_off = ms[i].data - b.comp_off;
+                    d.in_len = ms[i].clen;
+                    d.isize = ms[i].isize;
+                    d.crc = ms[i].crc;
+                }
+                bw.comp[m] = stages[(size_t)w.stage]->buf[m].data();
+                bw.comp_bytes[m] = b.comp_bytes;
+                bw.m[m] = bz_desc[m].data();
+                bw.members[m] = (uint32_t)(b.end - b.first);
+                bw.skip[m] = b.skip;
+                bw.n[m] = w.n[m];
+            }
+            const auto q0 = std::chrono::steady_clock::now();
+            const int qrc = fq_engine_raw_enqueue_bgzf(e, &bw);
+            raw_enqueue_s += since(q0);
+            if (qrc != FQ_OK) {
+                free_stages.push(w.stage);
+                throw std::runtime_error(std::string("fq_engine_raw_enqueue_bgzf: ") + fq_engine_last_error(e));
+            }
+            for (int m = 0; m < mates; ++m) bgzf_members[m] += bw.members[m];
+            wins.push_back(w);
+        };
         auto enqueue_window = [&](const Win& w) {  // (stage -1: an empty window)
+            if (bgzf_in && w.stage >= 0) return enqueue_bgzf_window(w);
             fq_raw_window rw{};
             for (int m = 0; m < mates; ++m) {
                 rw.bytes[m] = w.stage >= 0 ? stages[(size_t)w.stage]->buf[m].data() + off0 : nullptr;
@@ -2097,7 +2159,7 @@ struct Lane {
                     if (r.stop || (r.pairs == 0 && exhausted) || last) {
                         rr.done = last && !left && !r.stop && !failed;
                         raw_end = rr.done ? "end of input"
-                                          : std::string(r.stop ? "irregular record" : failed && last ? "gzip read failed ahead" : r.pairs == 0 ? "no pairs" : "bytes left at the end") +
+                                          : std::string(r.stop == FQ_RAW_STOP_INFLATE ? "a BGZF member did not inflate" : r.stop ? "irregular record" : failed && last ? "gzip read failed ahead" : r.pairs == 0 ? "no pairs" : "bytes left at the end") +
                                                 " after pack " + std::to_string(seq - 1) + " (window bytes " + std::to_string(w.n[0]) + "/" +
                                                 std::to_string(w.n[1]) + ", carry " + std::to_string(r.carry[0]) + "/" +
                                                 std::to_string(r.carry[1]) + ", max_len " + std::to_string(r.max_len) + ")";
@@ -2131,6 +2193,7 @@ struct Lane {
             if (mp[m]) munmap(const_cast<char*>(mp[m]), (size_t)size[m]);
         rr.next_seq = seq;
         rr.pairs = raw_pairs;
+        if (bgzf_in) raw_end += " (BGZF inputs: windows of whole 1 MiB reads inflated on the device)";
         if (gz_in) raw_end += " (gzip inputs inflated on " + std::to_string(gz_inflate_threads()) + " threads each)";
         return rr;
     }
@@ -2703,13 +2766,44 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
         // inflater -- RawMulti reads windows with pread, plain files only)
         // (split runs on several engines: text packs, whose first global record index the reader knows;
         // RawMulti's engines learn a window's pairs only at its launch turn)
+        // FQ_GZ_IN_DEVICE=2: BGZF inputs go through the raw stream too, their windows inflated on the
+        // device (one engine, every input a BGZF chain of members the device takes, every 1 MiB read of
+        // every chain within the engine's member cap and the window capacity; anything else keeps
+        // today's route).  A window holds at most 1024 members across the mates, what the chip inflates
+        // in one round (measured: DESIGN 7); FQ_BGZF_WINDOW_MEMBERS (profiling) sets another cap, 0 the
+        // engine's own.
+        std::unique_ptr<BgzfPlanner> bgzf_plan[2];
+        {
+            const char* gzi_env = std::getenv("FQ_GZ_IN_DEVICE");
+            bool ok = gzi_env && std::string(gzi_env) == "2" && fq_engine_raw_enqueue_bgzf && text_mode && raw_ok && G == 1 &&
+                      !o.interleaved && !(raw_env && std::string(raw_env) == "0") && gz_both;
+            const int mates = paired ? 2 : 1;
+            const char* wm_env = std::getenv("FQ_BGZF_WINDOW_MEMBERS");
+            const uint64_t wm = wm_env ? std::strtoull(wm_env, nullptr, 10) : 1024;
+            const uint32_t member_cap = wm ? (uint32_t)std::min<uint64_t>(FQ_RAW_BGZF_MEMBERS, std::max<uint64_t>(1, wm / (uint64_t)mates))
+                                           : (uint32_t)FQ_RAW_BGZF_MEMBERS;
+            const std::string files[2] = {o.in1, o.in2};
+            for (int m = 0; m < mates && ok; ++m) {
+                std::vector<BgzfChainMember> ms;
+                bool fits = false;
+                ok = bgzf_chain_members(files[m], ms, &fits) && fits;
+                if (!ok) break;
+                bgzf_plan[m].reset(new BgzfPlanner(std::move(ms), (uint64_t)1 << 20, Lane::raw_window_cap((int)pack_n, est), member_cap));
+                ok = bgzf_plan[m]->size() > 0 && bgzf_plan[m]->fits();
+            }
+            if (!ok) bgzf_plan[0].reset(), bgzf_plan[1].reset();
+        }
+        const bool bgzf_raw = bgzf_plan[0] != nullptr;
         const bool raw_mode = text_mode && raw_ok && !(split && G > 1) && !o.interleaved && !(raw_env && std::string(raw_env) == "0") &&
                               ((!ends_with_gz(o.in1) && (!paired || !ends_with_gz(o.in2)) && pr.mapped()) ||
-                               (gz_both && G == 1 && pr.parallel_gz()));
+                               (gz_both && G == 1 && (bgzf_raw || pr.parallel_gz())));
         std::promise<Lane::RawResume> raw_p;
         std::shared_future<Lane::RawResume> raw_f = raw_p.get_future().share();
         if (raw_mode && G == 1)
-            for (int m = 0; m < 2; ++m) lanes[0]->pre_gz[m] = std::move(pre_gz[m]);
+            for (int m = 0; m < 2; ++m) {
+                lanes[0]->pre_gz[m] = std::move(pre_gz[m]);
+                lanes[0]->bgzf[m] = std::move(bgzf_plan[m]);
+            }
         // several engines: one window source cutting whole pairs, dealt round-robin (RawMulti)
         std::unique_ptr<RawMulti> rm;
         std::thread rm_reader, rm_warmer;
@@ -3008,7 +3102,13 @@ int run_tool(int argc, char** argv, bool exit_when_done) {
             (o.ora && ora_devices_given > 1 ? "; --ora: one engine on device " + std::to_string(devices[0]) + " of the " +
                                                   std::to_string(ora_devices_given) + " given (the sampling counts one stream)"
                                             : std::string()) +
-            (gz_device ? "; device BGZF" : ""));
+            (gz_device ? "; device BGZF" : "") +
+            (bgzf_raw ? "; BGZF inputs inflated on the device: " + std::to_string(lanes[0]->bgzf_members[0] + lanes[0]->bgzf_members[1]) + " members"
+                      : std::string()));
+        if (bgzf_raw && std::getenv("FQ_TIMING"))
+            for (int m = 0; m < (paired ? 2 : 1); ++m)
+                std::fprintf(stderr, "bgzf input %s: %llu members inflated on the device, 0 on the host\n", (m ? o.in2 : o.in1).c_str(),
+                             (unsigned long long)lanes[0]->bgzf_members[m]);
         if (std::getenv("FQ_TIMING_MONO")) {  // (profiling: steady-clock stamps, to time exec and exit from outside)
             auto mono = [](std::chrono::steady_clock::time_point t) {
                 return std::to_string(std::chrono::duration<double>(t.time_since_epoch()).count());

@@ -410,7 +410,8 @@ int fq_engine_submit_text(fq_engine* e, const fq_text_batch* tb, fq_read_result*
  * (optional), fq_engine_raw_launch (window k: waits for its index), poll as for other packs.  At
  * most three windows are enqueued and not launched, and eight windows are in the engine (enqueued,
  * launched or not yet polled: a ninth enqueue waits for the oldest pack's copies); a window's
- * host bytes must stay valid until its pack is reported by fq_engine_poll.  Options as for text
+ * host bytes (of either enqueue call) may be reused once fq_engine_raw_wait or the launch of that
+ * window has returned: its copies are done by then.  Options as for text
  * packs (-m writes the merged stream into out->text.text[0], which must then hold both mates' window
  * and carry bytes + 28 * max_batch + 64; no -c, UMI, --discard_unmerged: those go
  * through fq_engine_raw_launch_routed below; the index filter and --phred64 as for text packs).
@@ -462,6 +463,37 @@ int fq_engine_raw_wait(fq_engine* e, fq_raw_result* r);
  * host bytes may then be reused) and drops them; launched packs are polled as usual.  The engine
  * takes other packs, or a new fq_engine_raw_begin once nothing is in flight. */
 int fq_engine_raw_end(fq_engine* e);
+
+/* A window whose bytes are BGZF members, inflated on the device (inflate.hip, "device inflate"
+ * below) straight into the window's place: only the compressed bytes cross PCIe.  The call stands
+ * where fq_engine_raw_enqueue stands in the protocol, and the two may be mixed window by window;
+ * wait, launch, poll and end are unchanged.  Mate m's members inflate back to back, the first at
+ * `skip` bytes before the window's first byte (they land in the tail of the carry region, which the
+ * carried bytes then overwrite), so the window is inflated bytes [skip, skip + n) of the members; a
+ * window may start and end inside a member, and what the last member holds past skip + n is ignored
+ * (the next window brings that member again).  The device buffers for the compressed bytes are made
+ * at the first such call.
+ * Refused (FQ_E_INVALID, nothing copied or launched, the engine stays usable): a call outside a raw
+ * stream or with three windows waiting; members[m] > FQ_RAW_BGZF_MEMBERS; a member whose in_len or
+ * isize exceeds FQ_INFLATE_MAX or whose payload is not within comp[m][0, comp_bytes[m]);
+ * comp_bytes[m] above the window capacity; skip[m] above the carry capacity, or a carry capacity
+ * below 65536; sum(isize) < skip + n, or sum(isize) - skip above the window capacity.
+ * A member that is not FQ_INFL_OK: fq_engine_raw_wait and the launch of that window report
+ * stop = FQ_RAW_STOP_INFLATE, pairs = 0 and carry[m] = the carried bytes + n[m] (nothing of the
+ * window is taken: the caller resumes with its own reader at window end - carry, which reports the
+ * error); windows enqueued behind it report the same and are dropped by fq_engine_raw_end. */
+#define FQ_RAW_BGZF_MEMBERS 8192           /* members per mate and window */
+#define FQ_RAW_STOP_INFLATE 2              /* fq_raw_result.stop: a member of the window was not FQ_INFL_OK */
+struct fq_inflate_member;
+typedef struct fq_raw_bgzf_window {
+    const void* comp[2];            /* mate m's compressed bytes (page-locked: asynchronous copy) */
+    uint64_t comp_bytes[2];         /* <= the window capacity of fq_engine_raw_begin */
+    const struct fq_inflate_member* m[2];  /* in_off relative to comp[m]; status / produced are ignored */
+    uint32_t members[2];            /* <= FQ_RAW_BGZF_MEMBERS */
+    uint32_t skip[2];               /* leading inflated bytes that are not part of the window */
+    uint64_t n[2];                  /* the window's bytes: inflated bytes [skip, skip + n) */
+} fq_raw_bgzf_window;
+int fq_engine_raw_enqueue_bgzf(fq_engine* e, const fq_raw_bgzf_window* w);
 
 /* Page-locked host memory for packs and records (portable across devices; transparent huge
  * pages registered with the runtime, hipHostMalloc as fallback).  FQ_E_NO_DEVICE without a HIP
