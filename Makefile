@@ -15,7 +15,7 @@ OBJDIR     := build/obj
 
 ENGINE_SRCS := $(CSRC)/engine.hip $(CSRC)/pe_kernel.hip $(CSRC)/pe_fast.hip $(CSRC)/pe_fast_long.hip $(CSRC)/synth.hip $(CSRC)/dup.hip $(CSRC)/kmer.hip $(CSRC)/kstat.hip $(CSRC)/ora.hip $(CSRC)/text.hip $(CSRC)/raw.hip $(CSRC)/deflate.hip $(CSRC)/inflate.hip $(CSRC)/ingest.hip
 ENGINE_OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(ENGINE_SRCS))
-ENGINE_HDRS := include/fqengine.h $(CSRC)/engine_internal.h $(CSRC)/device_ops.h $(CSRC)/deflate_core.h $(CSRC)/crc_core.h $(CSRC)/inflate_core.h $(CSRC)/kstat_core.h $(CSRC)/ora_core.h $(CSRC)/egress_core.h $(CSRC)/ingest_core.h
+ENGINE_HDRS := include/fqengine.h $(CSRC)/engine_internal.h $(CSRC)/device_ops.h $(CSRC)/deflate_core.h $(CSRC)/crc_core.h $(CSRC)/inflate_core.h $(CSRC)/kstat_core.h $(CSRC)/ora_core.h $(CSRC)/egress_core.h $(CSRC)/ingest_core.h $(CSRC)/tile_claim.h
 $(OBJDIR)/pe_fast_long.o: $(CSRC)/pe_fast.hip
 
 CXX        ?= g++

@@ -28,8 +28,9 @@ static bool prof_no_egress() {
 // Tile list the fast kernel hands to the general kernel (one per concurrently running launch).
 struct Scratch {
     int* slow_tiles = nullptr;
-    int* slow_count = nullptr;
+    int* slow_count = nullptr;  // [0] the list's length, [1] the fast kernel's tile claim counter
     size_t slow_cap = 0;
+    int* tile_ctr() const { return slow_count + 1; }
 };
 
 // One in-flight pack of the asynchronous pipeline (fq_engine_submit / fq_engine_poll): its own
@@ -220,7 +221,7 @@ static int validate_params(const fq_params* p, std::string& why) {
 }
 
 static int ensure_scratch(fq_engine* e, Scratch& sc, size_t ntiles, bool sync_device) {
-    if (!sc.slow_count) HIP_TRY(e, hipMalloc(&sc.slow_count, sizeof(int)));
+    if (!sc.slow_count) HIP_TRY(e, hipMalloc(&sc.slow_count, 2 * sizeof(int)));
     if (ntiles <= sc.slow_cap) return FQ_OK;
     // the old list may still be read by a launch in flight
     if (sync_device) HIP_TRY(e, hipDeviceSynchronize());
@@ -437,9 +438,9 @@ static int launch(fq_engine* e, const fq_batch& db, fq_read_result* dres, hipStr
         const size_t nitems = (size_t)db.n + 64 + 1;
         int rc = ensure_scratch(e, sc, nitems, sync_device_on_grow);
         if (rc != FQ_OK) return rc;
-        HIP_TRY(e, hipMemsetAsync(sc.slow_count, 0, sizeof(int), s));
+        HIP_TRY(e, hipMemsetAsync(sc.slow_count, 0, 2 * sizeof(int), s));  // (both counters, every launch)
         if (timed) HIP_TRY(e, hipEventRecord(e->ev0, s));
-        HIP_TRY(e, fq_launch_pe_fast(e->p, db, dres, e->acc, sc.slow_tiles, sc.slow_count, e->xfix, e->cus, s));
+        HIP_TRY(e, fq_launch_pe_fast(e->p, db, dres, e->acc, sc.slow_tiles, sc.slow_count, sc.tile_ctr(), e->xfix, e->cus, s));
         HIP_TRY(e, fq_launch_xfix_fold(e->acc + fq_acc_stats_offset(e->p.insert_size_max, e->p.max_cycles, 0), e->xfix,
                                        e->p.max_cycles, s));
         // (the hand-off list's length is known on the device only: as many workgroups as the

@@ -42,6 +42,7 @@
 
 #include "device_ops.h"
 #include "engine_internal.h"
+#include "tile_claim.h"
 
 using namespace fqdev;
 
@@ -973,6 +974,11 @@ __device__ __forceinline__ void count_by_value(unsigned long long* base, bool on
 // fq_debug_phase_cycles().
 constexpr int kPhases = 8;  // staging, trim, polyG, overlap, polyX/maxlen, filter, stats, store
 __device__ unsigned long long g_phase_cycles[kPhases];
+// and, per wave of the grid (block * waves per block + wave), the device's constant-rate clock
+// (wall_clock64, the same counter on every XCD) at the wave's start and at the end of its tile loop,
+// before the flush (tools/ablate.py --phases reads them with fq_debug_wave_ends())
+constexpr int kStampWaves = 8192;
+__device__ unsigned long long g_wave_clock[2 * kStampWaves];
 
 __device__ __forceinline__ void hadd(uint32_t* base, int word, unsigned long long v) {
     atomicAdd(reinterpret_cast<unsigned long long*>(base + word), v);
@@ -1131,12 +1137,23 @@ __device__ inline bool correct_pair_fast(const fq_params& p, uint32_t* col, uint
     /* (i+1)/per as ((i+1)*inv) >> 16, exact while per * (kMaxLen + 1) < 65536; else inv = 0: division */ \
     [[maybe_unused]] const int g_inv = g_per * (kMaxLen + 1) < 65536 ? (65536 + g_per - 1) / g_per : 0;
 
+// The tile claim's kernel argument (tile_claim.h): T0 and the grid's wave count, worked out by the
+// host, and the launch's counter.
+struct TileClaim {
+    int* ctr;
+    int t0, waves;
+};
+// (the kernel's first three arguments at their ABI offsets in the kernarg segment: p at 0, each of the
+// others at the next multiple of its alignment)
+constexpr size_t kBatchArg = (sizeof(fq_params) + alignof(fq_batch) - 1) & ~(alignof(fq_batch) - 1);
+constexpr size_t kClaimArg = (kBatchArg + sizeof(fq_batch) + alignof(TileClaim) - 1) & ~(alignof(TileClaim) - 1);
+
 // XTRA: the -c / UMI / -e instantiation of the full variants (kept apart so the other variants'
 // register allocation does not carry that code)
 // FIX: rows of exactly kChunks chunks (the batch stride is the column length: 160, or 320 in the long
 // build), so every per-chunk offset and bound is a compile-time constant
 template <bool LEAN, bool PAIRED, bool MERGE, bool XTRA = false, bool FIX = false>
-__global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __attribute__((amdgpu_waves_per_eu(Layout<LEAN, MERGE, PAIRED>::kWavesPerEU))) pe_fast_kernel(fq_params p, fq_batch b, fq_read_result* __restrict__ res,
+__global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __attribute__((amdgpu_waves_per_eu(Layout<LEAN, MERGE, PAIRED>::kWavesPerEU))) pe_fast_kernel(fq_params p, fq_batch b, TileClaim tc, fq_read_result* __restrict__ res,
                                                          unsigned long long* __restrict__ acc, int* __restrict__ slow_tiles,
                                                          int* __restrict__ slow_count, unsigned long long* __restrict__ xfix) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -1201,6 +1218,8 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
     const bool stamps = p.reserved[1] != 0;
     unsigned long long ph[kPhases] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long t_last = stamps ? clock64() : 0;
+    const int wave_id = blockIdx.x * kWaves + wave;
+    if (stamps && lane == 0 && wave_id < kStampWaves) g_wave_clock[2 * wave_id] = wall_clock64();
 #define FQ_STAMP(i)                                \
     if (stamps) {                                  \
         const unsigned long long now_ = clock64(); \
@@ -1215,18 +1234,29 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
     // read only on the rare hand-off path)
     constexpr int kItems = PAIRED ? 32 : 64;
     constexpr int kHole = 0x7FFFFFFF;
-    for (int t = blockIdx.x * kWaves + wave; t < ntiles; t += gridDim.x * kWaves) {
+    // Tiles below T0 go round the grid's waves in a fixed stride; the launch's last tiles are claimed
+    // from the launch's counter, kClaimTiles at a time (tile_claim.h), so that no wave is left with a
+    // long tile list while others have none.  The claim is issued at the end of a tile and consumed at
+    // once, and its three words (tc: T0 and the grid's wave count from the host, the counter) are re-read
+    // from the kernarg segment there, like the parameters below: nothing of it lives across the tile body.
+    auto claim_tile = [&](const TileClaim& c) -> int {
+        int v = 0;
+        if (lane == 0) v = atomicAdd(c.ctr, 1);
+        return fq_claimed_tile(c.t0, __builtin_amdgcn_readfirstlane(v));
+    };
+    int t = blockIdx.x * kWaves + wave;
+    if (t >= tc.t0) t = claim_tile(tc);
+    while (t < ntiles) {
         // The parameters and the batch descriptor are re-read from the kernarg segment every tile
         // (scalar loads, cached): kept live across the tile loop they overflow the SGPR file, and the
         // spills cost VALU (v_writelane / v_readlane) and scratch traffic inside the loop.
         typedef const __attribute__((address_space(4))) fq_params KParams;
         typedef const __attribute__((address_space(4))) fq_batch KBatch;
-        // (the kernel's first two arguments, at their ABI offsets in the kernarg segment: p at 0, b at
-        // the next multiple of its alignment; taking &p instead would copy p to scratch)
+        // (kBatchArg: b's offset in the kernarg segment; taking &p instead would copy p to scratch)
         const __attribute__((address_space(4))) char* ka_ =
             (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
         KParams* kp_ = (KParams*)ka_;
-        KBatch* kb_ = (KBatch*)(ka_ + ((sizeof(fq_params) + alignof(fq_batch) - 1) & ~(alignof(fq_batch) - 1)));
+        KBatch* kb_ = (KBatch*)(ka_ + kBatchArg);
         asm volatile("" : "+s"(kp_), "+s"(kb_));
         const fq_params& p = *(const fq_params*)kp_;
         const fq_batch& b = *(const fq_batch*)kb_;
@@ -2321,7 +2351,17 @@ __global__ void __launch_bounds__((Layout<LEAN, MERGE, PAIRED>::kThreads)) __att
                 __builtin_nontemporal_store(u32x4_t{w.x, w.y, w.z, w.w},
                                             reinterpret_cast<u32x4_t*>(&res[PAIRED ? 2 * (size_t)idx + mate : (size_t)idx]));
         }
+        // the wave's next tile: the next round of the strided part, or a claim
+        typedef const __attribute__((address_space(4))) TileClaim KClaim;
+        KClaim* kc_ = (KClaim*)(ka_ + kClaimArg);
+        asm volatile("" : "+s"(kc_));
+        const TileClaim& c = *(const TileClaim*)kc_;
+        const int nx = fq_next_tile(t, c.t0, c.waves);
+        t = nx >= 0 ? nx : claim_tile(c);
     }
+#ifdef FQ_PHASE_STAMPS
+    if (stamps && lane == 0 && wave_id < kStampWaves) g_wave_clock[2 * wave_id + 1] = wall_clock64();
+#endif
     if (lane < hres[2 * wave + 1]) slow_tiles[hres[2 * wave] + lane] = kHole;  // the rest of the last reservation
 
     FQ_STAMP(7)
@@ -2438,6 +2478,12 @@ extern "C" __attribute__((visibility("default"))) int fq_debug_phase_cycles(unsi
     for (int i = 0; i < n && i < kPhases; ++i) out[i] = h[i];
     return 0;
 }
+// and the waves' start / loop-end clocks: out[2 w], out[2 w + 1] for wave w < n (zero: not stamped)
+extern "C" __attribute__((visibility("default"))) int fq_debug_wave_ends(unsigned long long* out, int n) {
+    if (n < 0 || n > kStampWaves) return -1;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_clock), 2 * (size_t)n * sizeof(unsigned long long)) != hipSuccess) return -3;
+    return 0;
+}
 #define FQ_PREPARE fq_pe_fast_prepare
 #define FQ_LAUNCH fq_launch_pe_fast
 #else  // the long-read build (pe_fast_long.hip)
@@ -2477,25 +2523,28 @@ hipError_t FQ_PREPARE() {
 
 template <bool LEAN, bool PAIRED, bool MERGE, bool XTRA>
 static void launch_variant(const fq_params& p, const fq_batch& b, fq_read_result* res, unsigned long long* acc,
-                           int* slow_tiles, int* slow_count, unsigned long long* xfix, int grid, int extra_lds,
-                           hipStream_t stream) {
+                           int* slow_tiles, int* slow_count, int* tile_ctr, unsigned long long* xfix, int grid,
+                           int extra_lds, hipStream_t stream) {
     using LY = Layout<LEAN, MERGE, PAIRED>;
     const dim3 g(grid * LY::kBlocksPerCU), t(LY::kThreads);
     const size_t lds = LY::kLdsW * 4 + extra_lds;
+    const int ntiles = PAIRED ? (b.n + 31) >> 5 : (b.n + 63) >> 6, waves = (int)g.x * LY::kWaves;
+    const TileClaim tc{tile_ctr, fq_static_end(ntiles, waves), waves};
     if (b.stride == 16 * kChunks)
-        hipLaunchKernelGGL((pe_fast_kernel<LEAN, PAIRED, MERGE, XTRA, true>), g, t, lds, stream, p, b, res, acc, slow_tiles,
-                           slow_count, xfix);
+        hipLaunchKernelGGL((pe_fast_kernel<LEAN, PAIRED, MERGE, XTRA, true>), g, t, lds, stream, p, b, tc, res, acc,
+                           slow_tiles, slow_count, xfix);
     else
-        hipLaunchKernelGGL((pe_fast_kernel<LEAN, PAIRED, MERGE, XTRA, false>), g, t, lds, stream, p, b, res, acc, slow_tiles,
-                           slow_count, xfix);
+        hipLaunchKernelGGL((pe_fast_kernel<LEAN, PAIRED, MERGE, XTRA, false>), g, t, lds, stream, p, b, tc, res, acc,
+                           slow_tiles, slow_count, xfix);
 }
 
 hipError_t FQ_LAUNCH(const fq_params& p, const fq_batch& b, fq_read_result* res, unsigned long long* acc,
-                     int* slow_tiles, int* slow_count, unsigned long long* xfix, int grid, hipStream_t stream) {
+                     int* slow_tiles, int* slow_count, int* tile_ctr, unsigned long long* xfix, int grid,
+                     hipStream_t stream) {
 #if FQ_MAXLEN == 160
     // rows longer than 160 bytes: the 320-position build (reads beyond 320 bp are handed off per tile)
     if (b.stride > kMaxLen)
-        return fq_launch_pe_fast_long(p, b, res, acc, slow_tiles, slow_count, xfix, grid, stream);
+        return fq_launch_pe_fast_long(p, b, res, acc, slow_tiles, slow_count, tile_ctr, xfix, grid, stream);
 #endif
     const bool lean = p.trim_front1 == 0 && p.trim_tail1 == 0 && p.trim_front2 == 0 && p.trim_tail2 == 0 &&
                       !(p.avg_qual_limit > 0) &&
@@ -2506,22 +2555,22 @@ hipError_t FQ_LAUNCH(const fq_params& p, const fq_batch& b, fq_read_result* res,
     const bool xtra = p.correction_enabled || p.umi_front1 > 0 || p.umi_front2 > 0 || p.avg_qual_limit > 0;
     const int pad = p.reserved[2] > 0 && p.reserved[2] <= 4096 ? p.reserved[2] : 0;  // profiling: extra LDS (LEAN)
     if (p.merge_enabled && xtra)  // -c / UMI / -e with -m
-        launch_variant<false, true, true, true>(p, b, res, acc, slow_tiles, slow_count, xfix, grid, 0, stream);
+        launch_variant<false, true, true, true>(p, b, res, acc, slow_tiles, slow_count, tile_ctr, xfix, grid, 0, stream);
     else if (p.merge_enabled)
-        launch_variant<false, true, true, false>(p, b, res, acc, slow_tiles, slow_count, xfix, grid, 0, stream);
+        launch_variant<false, true, true, false>(p, b, res, acc, slow_tiles, slow_count, tile_ctr, xfix, grid, 0, stream);
     else
     if (p.paired && lean)
-        launch_variant<true, true, false, false>(p, b, res, acc, slow_tiles, slow_count, xfix, grid, pad, stream);
+        launch_variant<true, true, false, false>(p, b, res, acc, slow_tiles, slow_count, tile_ctr, xfix, grid, pad, stream);
     else if (p.paired && xtra)
-        launch_variant<false, true, false, true>(p, b, res, acc, slow_tiles, slow_count, xfix, grid, 0, stream);
+        launch_variant<false, true, false, true>(p, b, res, acc, slow_tiles, slow_count, tile_ctr, xfix, grid, 0, stream);
     else if (p.paired)
-        launch_variant<false, true, false, false>(p, b, res, acc, slow_tiles, slow_count, xfix, grid, 0, stream);
+        launch_variant<false, true, false, false>(p, b, res, acc, slow_tiles, slow_count, tile_ctr, xfix, grid, 0, stream);
     else if (lean)
-        launch_variant<true, false, false, false>(p, b, res, acc, slow_tiles, slow_count, xfix, grid, pad, stream);
+        launch_variant<true, false, false, false>(p, b, res, acc, slow_tiles, slow_count, tile_ctr, xfix, grid, pad, stream);
     else if (xtra)
-        launch_variant<false, false, false, true>(p, b, res, acc, slow_tiles, slow_count, xfix, grid, 0, stream);
+        launch_variant<false, false, false, true>(p, b, res, acc, slow_tiles, slow_count, tile_ctr, xfix, grid, 0, stream);
     else
-        launch_variant<false, false, false, false>(p, b, res, acc, slow_tiles, slow_count, xfix, grid, 0, stream);
+        launch_variant<false, false, false, false>(p, b, res, acc, slow_tiles, slow_count, tile_ctr, xfix, grid, 0, stream);
     return hipGetLastError();
 }
 #undef FQ_PREPARE

@@ -20,6 +20,8 @@ variants = [("full", 0), ("no_overlap", 1), ("no_filter", 2), ("no_stats", 4), (
             ("no_lds_atomics", 16), ("no_overlap_filter_stats", 7), ("stage_only", 15), ("no_polyg_counters", 32),
             ("no_ov_exact", 64), ("no_ov_scan", 128),
             ("plus_512_valu", 256), ("one_wg_per_cu", 70 << 16)]
+if "--phases" in sys.argv:  # only the stamped launch below (phase shares, the waves' end times)
+    variants = []
 only = os.environ.get("VARIANTS")
 if only:
     variants = [v for v in variants if v[0] in only.split(",")]
@@ -60,4 +62,34 @@ if tot == 0:
     print("no phase stamps (build with make STAMPS=1)")
 for nm, v in (zip(names, out) if tot else []):
     print(f"phase {nm:14s} {100.0 * v / tot:6.1f}%  {v / 2048:14.0f} cycles/wave")
+
+# The waves' clocks (device clock at 100 MHz) at their start and at the end of their tile loops, before
+# the flush: how long the launch's SIMDs wait for its last waves.  Relative to the launch's first
+# start stamp and last end stamp; per XCD (workgroup index % 8) as well.
+import numpy as np
+NW = 8192
+ws = np.zeros(2 * NW, np.uint64)
+lib.fq_debug_wave_ends.argtypes = [ctypes.c_void_p, ctypes.c_int]
+if tot and lib.fq_debug_wave_ends(ws.ctypes.data, NW) == 0:
+    start, end = ws[0::2].astype(np.int64), ws[1::2].astype(np.int64)
+    on = end > 0
+    nw = int(on.sum())
+    start, end = start[on], end[on]
+    wg_waves = int(os.environ.get("WG_WAVES", 8))  # waves per workgroup of the variant run (C3: 8)
+    xcd = (np.nonzero(on)[0] // wg_waves) % 8
+    t0, t1 = int(start.min()), int(end.max())
+    span = t1 - t0
+    us = lambda ticks: ticks / 100.0
+    rel = end - t0
+    q = lambda v, f: float(np.quantile(v, f))
+    print(f"waves {nw}  launch span (first start to last loop end) {us(span):.1f} us  start spread {us(int(start.max()) - t0):.1f} us")
+    print(f"loop end, us after the first start: min {us(rel.min()):.1f}  median {us(q(rel, 0.5)):.1f}  p99 {us(q(rel, 0.99)):.1f}  max {us(rel.max()):.1f}")
+    idle = t1 - end
+    print(f"idle before the last wave's end: mean {us(idle.mean()):.1f} us = {100.0 * idle.mean() / span:.2f}% of the span, "
+          f"median {us(q(idle, 0.5)):.1f} us, max {us(idle.max()):.1f} us = {100.0 * idle.max() / span:.2f}%")
+    for x in range(8):
+        r = rel[xcd == x]
+        if r.size:
+            print(f"  XCD {x}: waves {r.size:5d}  end min {us(r.min()):9.1f}  median {us(q(r, 0.5)):9.1f}  max {us(r.max()):9.1f}  "
+                  f"mean idle {100.0 * (t1 - end[xcd == x]).mean() / span:.2f}%")
 lib.fq_engine_destroy(h)
